@@ -1,13 +1,15 @@
 #!/usr/bin/env python
-"""bench.py -- training images/s of MedT (3x128x128) on N MI355X, plus the attention-kernel roofline
-and the CPU baseline.  Contract: see the task description / DESIGN.md "Measurement".
+"""bench.py -- training images/s of MedT (3x128x128) on N MI355X; with --full also the eval-forward timings, the
+attention-kernel roofline, the CPU baseline and the box probe.  Contract: see DESIGN.md "Measurement".
 
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A step = forward + cross-entropy + backward + (N>1: gradient all-reduce) + Adam on one synthetic batch
 already resident in HBM (reference train.py:140,156-161).  Weak scaling: 4 images per GPU.
+A plain run sets up, warms up, times exactly --steps steps, writes --dump-outputs and prints the result line; everything
+else it measures runs only under --full.
 """
 from __future__ import annotations
 
@@ -286,6 +288,35 @@ def baseline_config(args):
             ("MedT", 256, 2, "f32"): "configs[4]'s per-GPU shard"}.get(key, "(not a BASELINE.json configuration)")
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(outdir, loss, model):
+    """--dump-outputs DIR: what a caller of the timed step holds after its last step -- the loss the step returns
+    (`loss.npy`, float64) and the parameters and buffers it updated in place (`param.<name>.npy`, `buffer.<name>.npy`:
+    float32, integer buffers as float64).  Above DUMP_BUDGET_BYTES in all, every tensor larger than 4096 elements is cut
+    to a fixed, seeded sample of its flattened elements (the same indices for the same model on every run)."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"loss": loss.detach().double().reshape(1).cpu()}
+    for prefix, items in (("param", model.named_parameters()), ("buffer", model.named_buffers())):
+        for k, t in items:
+            t = t.detach()
+            arrays[f"{prefix}.{k}"] = (t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()).cpu()
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        keep = DUMP_BUDGET_BYTES / total
+        g = torch.Generator().manual_seed(0)
+        for k in sorted(arrays):
+            a = arrays[k].reshape(-1)
+            if a.numel() > 4096:
+                idx = torch.randint(a.numel(), (max(4096, int(a.numel() * keep) - 1),), generator=g).sort().values
+                arrays[k] = a[idx]
+    import numpy as np
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a.numpy())
+    log(f"outputs of the last timed step: {len(arrays)} arrays in {outdir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -298,8 +329,12 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
                     help="storage of the attention layers' saved activations (bf16 = BASELINE.json configs[1]); "
                          "arithmetic and statistics are f32 either way")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss and the updated parameters and buffers as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the repeat timing windows, eval-forward timings, attention-kernel roofline, CPU baseline and box probe")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the attention-kernel roofline")
     ap.add_argument("--roofline-only", action="store_true", help="only the attention-kernel microbenchmark (for rocprofv3)")
     args = ap.parse_args()
 
@@ -345,11 +380,9 @@ def main():
     for _ in range(args.warmup):
         step()
     log("warm-up done; timing")
-    # EXACTLY --steps steps per timed window, barrier + synchronize on both sides, MAX over ranks.  The window is ~50 ms at
-    # this step time, so one scheduler hiccup moves it by several percent: MEDT_BENCH_WINDOWS (default 5) back-to-back
-    # windows are timed and the MEDIAN window is the one reported (ms_per_step x steps == that window's wall time).
-    windows = []
-    for _ in range(max(1, int(os.environ.get("MEDT_BENCH_WINDOWS", "5")))):
+
+    def window():
+        """EXACTLY --steps steps, barrier + synchronize on both sides, MAX over ranks: (wall time, last step's loss)."""
         if distributed:
             dist.barrier()
         torch.cuda.synchronize()
@@ -364,10 +397,24 @@ def main():
             t = torch.tensor([el], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = t.item()
-        windows.append(el)
-    elapsed = sorted(windows)[len(windows) // 2]
+        return el, loss
+
+    # the headline: ONE window of --steps steps (ms_per_step x steps == its wall time)
+    elapsed, loss = window()
     final_loss = loss.item()
-    log(f"{args.steps} steps per window; windows (ms): {[round(w * 1e3, 2) for w in windows]}; median {elapsed * 1e3:.2f}")
+    log(f"{args.steps} steps: {elapsed * 1e3:.2f} ms")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
+    windows = [elapsed]
+    if args.full:
+        # The window is ~50 ms at this step time, so one scheduler hiccup moves it by several percent: --full times
+        # MEDT_BENCH_WINDOWS (default 5) back-to-back windows in all and reports the MEDIAN one beside the headline
+        # (`final_loss` is then the loss of the last window's last step).
+        for _ in range(max(1, int(os.environ.get("MEDT_BENCH_WINDOWS", "5"))) - 1):
+            el, loss = window()
+            windows.append(el)
+        final_loss = loss.item()
+        log(f"windows (ms): {[round(w * 1e3, 2) for w in windows]}; median {sorted(windows)[len(windows) // 2] * 1e3:.2f}")
 
     result = {
         "metric": f"training images/sec ({args.model}, 3x{args.imgsize}x{args.imgsize})", "value": world * args.batch * args.steps / elapsed,
@@ -389,7 +436,9 @@ def main():
         # all-reduced where the global branch's backward ends (medt_amd.optim.TWO_BUCKETS)
         "gradient_buckets": [[hi - lo for lo, hi in g.bounds] for g in opt.groups],
     }
-    if rank == 0 and world == 1:
+    if args.full:
+        result["ms_per_step_median_window"] = sorted(windows)[len(windows) // 2] / args.steps * 1e3
+    if args.full and rank == 0 and world == 1:
         # BASELINE's second figure, "fwd ms/image": the eval-mode forward of reference test.py:106-119, replayed as a
         # hipGraph (medt_amd.trainer.InferStep, what test.py runs) at the bench batch and at test.py's batch of 1;
         # the eager launch-by-launch forward (host-bound) is reported beside it
@@ -454,9 +503,10 @@ def main():
             result["cpu_baseline"] = cpu_baseline_leg()
             result["vs_cpu_baseline"] = result["value"] / result["cpu_baseline"]["value"]
     if rank == 0:
-        # LAST: the probes run as child processes with their own HIP context; the eager eval forward measured right behind them
-        # read 2.0-2.6 ms/image instead of 0.7 (this process's queues had been switched out)
-        result["box_probe"] = box_probe()
+        if args.full:
+            # LAST: the probes run as child processes with their own HIP context; the eager eval forward measured right behind
+            # them read 2.0-2.6 ms/image instead of 0.7 (this process's queues had been switched out)
+            result["box_probe"] = box_probe()
         print(json.dumps(result))
     if dist.is_initialized():
         # Orderly teardown.  The captured hipGraph holds RCCL kernel nodes that reference the communicator: release the

@@ -76,7 +76,7 @@ if tr:
         k = re.sub(r"<.*", "", short(r["Kernel_Name"]))
         cnt[k] += 1
         busy[k] += int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
-    json.dump({"source": "rocprofv3 --kernel-trace on `python bench.py --no-cpu-baseline --no-roofline`: the launches between "
+    json.dump({"source": "rocprofv3 --kernel-trace on `python bench.py --full --no-cpu-baseline --no-roofline`: the launches between "
                          "two consecutive adam_step kernels of the replayed hipGraph (the profiler serialises the two "
                          "streams, so busy time is per kernel, not wall time)",
                "launches_per_step": len(step),
@@ -180,10 +180,10 @@ if os.path.exists(p):
         name, _, rest = line.partition(" ")
         try:
             j = json.loads(rest)
-            ab[name] = {"ms_per_step": j["ms_per_step"], "images_per_s": j["value"]}
+            ab[name] = {"ms_per_step": j.get("ms_per_step_median_window", j["ms_per_step"]), "images_per_s": j["value"]}
         except Exception:
             pass
-    json.dump({"what": "`python bench.py --no-cpu-baseline --no-roofline` (MedT 128, 4 images, one hipGraph replay per step) on ONE "
+    json.dump({"what": "`python bench.py --full --no-cpu-baseline --no-roofline` (MedT 128, 4 images, one hipGraph replay per step) on ONE "
                        "box, back to back, with one switch flipped (scripts/collect_profiles.sh lists the variables): "
                        "BN_FIN_APPLY_OFF = bn_finalize + bn_apply_act as two launches; BN_CHAN_OFF = bn_act_bwd_stats -> "
                        "bn_bwd_finalize -> bn_bwd_apply instead of one workgroup per (group, channel); WGRAD_R2_CHUNKS = round 2's "

@@ -344,6 +344,84 @@ def manifest():
     print("wrote state_manifest.json")
 
 
+def tensor_digest(t: torch.Tensor):
+    """[shape, dtype, sha256 of the bytes]: bit-identity of a tensor without storing it."""
+    import hashlib
+    t = t.detach().contiguous().cpu()
+    return [list(t.shape), str(t.dtype).replace("torch.", ""), hashlib.sha256(t.numpy().tobytes()).hexdigest()]
+
+
+GATE_CASES = [(cls_name, mode, width, stride) for cls_name, mode in (("AxialAttention_gated_sig", "sigmoid"),
+                                                                      ("AxialAttention_gated_data", "data"))
+              for width, stride in ((False, 1), (True, 2))]
+
+
+def gate_case_key(cls_name, width, stride):
+    return f"{cls_name}_{'w' if width else 'h'}_s{stride}"
+
+
+def gate_case_inputs(key, out_shape=None):
+    """x (3, 32, 12, 12) and the output weights w of one gate-variant case, float64, from a generator seeded by the case."""
+    g = torch.Generator().manual_seed(sum(ord(c) for c in key))
+    x = torch.randn(3, 32, 12, 12, generator=g, dtype=torch.float64)
+    return x if out_shape is None else (x, torch.randn(out_shape, generator=g, dtype=torch.float64))
+
+
+def reference_surface_fixtures():
+    """What tests/test_oracle_vs_reference.py, tests/test_module_surface.py and tests/test_metrics_cpu.py read from the
+    reference: reference_surface.json -- digests of the reference's initial state_dicts under fixed seeds (factories and
+    model_codes gate variants), key / requires_grad lists, classwise metrics on seeded inputs; gate_variants_fp64.npz -- the model_codes gate flavours (:215-313, :316-443)
+    executed in float64, training mode: state, output and every gradient."""
+    import json
+    mc = ref_loader.load_model_codes()
+    surf = {"init_seed1234_S128": {}, "gray_MedT_128_keys": list(ref_loader.factory("MedT")(img_size=128, imgchan=1).state_dict()),
+            "model_codes": {}}
+    for name in ("gatedaxialunet", "MedT"):
+        torch.manual_seed(1234)
+        ref = ref_loader.factory(name)(img_size=128, imgchan=3)
+        surf["init_seed1234_S128"][name] = [[k, *tensor_digest(v)] for k, v in ref.state_dict().items()]
+    for cls_name, seed, kw in (("AxialAttention_gated_sig", 9, dict(stride=2, width=True)),
+                               ("AxialAttention_gated_data", 10, dict(stride=1, width=False))):
+        torch.manual_seed(seed)
+        m = getattr(mc, cls_name)(32, 32, groups=8, kernel_size=16, **kw)
+        surf["model_codes"][cls_name] = {"seed": seed, "state": [[k, *tensor_digest(v)] for k, v in m.state_dict().items()],
+                                         "params": [[k, p.requires_grad] for k, p in m.named_parameters()]}
+    surf["model_codes"]["AxialBlock_gated_data_keys"] = list(mc.AxialBlock_gated_data(32, 16, kernel_size=16).state_dict())
+    # the reference's metrics.py (:23-57) on the inputs of tests/test_metrics_cpu.py (float32 values are exact in JSON)
+    ref_metrics = ref_loader.load_metrics()
+    torch.manual_seed(2)
+    out = torch.rand(3, 2, 9, 11)
+    gt = torch.randint(0, 2, (3, 9, 11))
+    surf["metrics_seed2"] = {f: [str(r.dtype).replace("torch.", ""), r.cpu().tolist()]
+                             for f in ("classwise_iou", "classwise_f1", "jaccard_index", "f1_score")
+                             for r in [getattr(ref_metrics, f)(out, gt)]}
+    with open(os.path.join(HERE, "reference_surface.json"), "w") as f:
+        json.dump(surf, f, separators=(",", ":"))
+    print("wrote reference_surface.json")
+    fx = {}
+    for cls_name, mode, width, stride in GATE_CASES:
+        key = gate_case_key(cls_name, width, stride)
+        torch.manual_seed(5)
+        layer = getattr(mc, cls_name)(32, 32, groups=8, kernel_size=12, stride=stride, width=width).double()
+        for p in layer.parameters():
+            if p.dim() == 0:
+                p.data.uniform_(-1, 1)
+            p.requires_grad_(True)
+        layer.train()
+        x = gate_case_inputs(key).requires_grad_(True)
+        out = layer(x)
+        _, w = gate_case_inputs(key, out.shape)
+        (out * w).sum().backward()
+        for k, v in layer.state_dict().items():             # after the forward: the state the oracle is handed
+            fx[f"{key}/state/{k}"] = v.detach().numpy()
+        fx[f"{key}/out"] = out.detach().numpy()
+        fx[f"{key}/x_grad"] = x.grad.numpy()
+        for k, p in layer.named_parameters():
+            fx[f"{key}/grad/{k}"] = p.grad.numpy()
+    np.savez_compressed(os.path.join(HERE, "gate_variants_fp64.npz"), **fx)
+    print("wrote gate_variants_fp64.npz", os.path.getsize(os.path.join(HERE, "gate_variants_fp64.npz")) // 1024, "KB")
+
+
 def main():
     """`python make_golden.py` regenerates everything; `python make_golden.py layer_gatedsig` only the fixtures whose
     file name starts with the given prefix (the others are deterministic re-runs of the same reference code)."""
@@ -352,6 +430,8 @@ def main():
     torch.set_num_threads(os.cpu_count())
     if not only:
         manifest()
+    if "reference_surface.json".startswith(only) or "gate_variants_fp64.npz".startswith(only):
+        reference_surface_fixtures()
     layer_cases = [
         ("gatedsig", 32, 16, True, 2, 2, 17),
         ("gatedsig", 16, 32, False, 1, 2, 18),

@@ -3,7 +3,6 @@ import pytest
 import torch
 
 import helpers as H
-from oracle import ref_loader
 
 
 def build(name, S, chan=3):
@@ -37,16 +36,16 @@ def test_public_names():
     assert ax.AxialBlock_dynamic.expansion == 2
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="reference checkout not present")
 @pytest.mark.parametrize("name", ["gatedaxialunet", "MedT"])
 def test_same_seed_same_init_as_reference(name):
-    torch.manual_seed(1234)
-    ref = ref_loader.factory(name)(img_size=128, imgchan=3)
+    """The reference's initial state under torch.manual_seed(1234), as per-tensor digests (tests/golden/reference_surface.json)."""
+    from test_oracle_vs_reference import digest, reference_surface
+    ref = reference_surface()["init_seed1234_S128"][name]
     torch.manual_seed(1234)
     mine = build(name, 128)
-    a, b = ref.state_dict(), mine.state_dict()
-    assert list(a.keys()) == list(b.keys())
-    for k in a:
-        assert torch.equal(a[k], b[k]), k
-    # a reference checkpoint loads strictly
-    mine.load_state_dict(ref.state_dict(), strict=True)
+    b = mine.state_dict()
+    assert [k for k, *_ in ref] == list(b.keys())
+    for k, *dg in ref:
+        assert dg == digest(b[k]), k
+    # a reference checkpoint (its keys, shapes and dtypes) loads strictly
+    mine.load_state_dict({k: torch.zeros(shape, dtype=getattr(torch, dt)) for k, shape, dt, _ in ref}, strict=True)

@@ -1,4 +1,9 @@
-"""Pin the oracle against the reference executed live (only where /root/reference exists)."""
+"""Pin the oracle against the reference: executed live where a reference checkout exists (whole networks, every gradient),
+and against what tests/golden/make_golden.py recorded from it everywhere (reference_surface.json, gate_variants_fp64.npz)."""
+import hashlib
+import json
+import os
+
 import pytest
 import torch
 
@@ -6,9 +11,19 @@ import helpers as H
 from oracle import medt_oracle as O
 from oracle import ref_loader
 
-pytestmark = pytest.mark.skipif(not ref_loader.available(), reason="reference checkout not present")
+
+def reference_surface():
+    with open(os.path.join(H.GOLDEN, "reference_surface.json")) as f:
+        return json.load(f)
 
 
+def digest(t):
+    """[shape, dtype, sha256 of the bytes] (tests/golden/make_golden.py::tensor_digest)."""
+    t = t.detach().contiguous().cpu()
+    return [list(t.shape), str(t.dtype).replace("torch.", ""), hashlib.sha256(t.numpy().tobytes()).hexdigest()]
+
+
+@pytest.mark.skipif(not ref_loader.available(), reason="reference checkout not present")
 @pytest.mark.parametrize("name,S,N", [("gatedaxialunet", 64, 2), ("axialunet", 64, 1), ("MedT", 128, 1), ("logo", 128, 1)])
 def test_model_forward_backward_fp64(name, S, N):
     torch.manual_seed(0)
@@ -42,60 +57,56 @@ def test_model_forward_backward_fp64(name, S, N):
 
 
 def test_reference_gray_and_manifest_agree():
-    m = ref_loader.factory("MedT")(img_size=128, imgchan=1)
+    keys = reference_surface()["gray_MedT_128_keys"]                # the reference's MedT(img_size=128, imgchan=1) state_dict keys
     ent = H.manifest()["MedT/128/1"]["state"]
-    assert [k for k, _, _ in ent] == list(m.state_dict().keys())
+    assert [k for k, _, _ in ent] == keys
 
 
 @pytest.mark.parametrize("cls_name,mode", [("AxialAttention_gated_sig", "sigmoid"), ("AxialAttention_gated_data", "data")])
 @pytest.mark.parametrize("width,stride", [(False, 1), (True, 2)])
 def test_gate_variants_fp64(cls_name, mode, width, stride):
     """The experimental gate flavours of the reference's model_codes.py (:215-313, :316-443) against the oracle's
-    gate_mode, forward + every gradient, training mode, executed live in fp64."""
-    mc = ref_loader.load_model_codes()
-    torch.manual_seed(5)
-    layer = getattr(mc, cls_name)(32, 32, groups=8, kernel_size=12, stride=stride, width=width).double()
-    for p in layer.parameters():
-        if p.dim() == 0:
-            p.data.uniform_(-1, 1)
-        p.requires_grad_(True)
-    layer.train()
-    x = torch.randn(3, 32, 12, 12, dtype=torch.float64, requires_grad=True)
-    out_ref = layer(x)
-    w = torch.randn_like(out_ref)
-    (out_ref * w).sum().backward()
-    st = O.clone_state({"L." + k: v for k, v in layer.state_dict().items()}, torch.float64, requires_grad=True)
-    xo = x.detach().clone().requires_grad_(True)
+    gate_mode, forward + every gradient, training mode, fp64 (the reference's results: tests/golden/gate_variants_fp64.npz,
+    make_golden.py::reference_surface_fixtures)."""
+    from golden.make_golden import gate_case_inputs, gate_case_key
+    key = gate_case_key(cls_name, width, stride)
+    fx = H.load_golden("gate_variants_fp64.npz")
+    pre = key + "/"
+    state = {k[len(pre + "state/"):]: torch.from_numpy(v) for k, v in fx.items() if k.startswith(pre + "state/")}
+    grads = {k[len(pre + "grad/"):]: torch.from_numpy(v) for k, v in fx.items() if k.startswith(pre + "grad/")}
+    out_ref, x_grad = torch.from_numpy(fx[pre + "out"]), torch.from_numpy(fx[pre + "x_grad"])
+    x, w = gate_case_inputs(key, out_ref.shape)
+    st = O.clone_state({"L." + k: v for k, v in state.items()}, torch.float64, requires_grad=True)
+    xo = x.clone().requires_grad_(True)
     out = O.axial_attention(xo, st, "L", width, stride, True, gate_mode=mode)
     (out * w).sum().backward()
     assert H.rel_err(out, out_ref) < 1e-10
-    assert H.rel_err(xo.grad, x.grad) < 1e-9
-    gmax = max(p.grad.abs().max().item() for p in layer.parameters() if p.grad is not None)
-    for k, p in layer.named_parameters():
-        assert (st["L." + k].grad - p.grad).abs().max().item() < 1e-9 * gmax, k
+    assert H.rel_err(xo.grad, x_grad) < 1e-9
+    gmax = max(g.abs().max().item() for g in grads.values())
+    assert grads and all(st["L." + k].requires_grad for k in grads)
+    for k, g in grads.items():
+        assert (st["L." + k].grad - g).abs().max().item() < 1e-9 * gmax, k
 
 
 def test_gated_sig_module_surface_matches_reference():
+    """The reference's side: initial state_dicts under the same seeds, as digests (reference_surface.json)."""
     import lib as droplib  # noqa: F401
     from lib.models import model_codes
-    mc = ref_loader.load_model_codes()
-    torch.manual_seed(9)
-    a = mc.AxialAttention_gated_sig(32, 32, groups=8, kernel_size=16, stride=2, width=True)
+    mc = reference_surface()["model_codes"]
     torch.manual_seed(9)
     b = model_codes.AxialAttention_gated_sig(32, 32, groups=8, kernel_size=16, stride=2, width=True)
-    sa, sb = a.state_dict(), b.state_dict()
-    assert list(sa.keys()) == list(sb.keys())
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), k                # same registration order -> same RNG stream -> same init
-    assert [(k, p.requires_grad) for k, p in a.named_parameters()] == [(k, p.requires_grad) for k, p in b.named_parameters()]
-    torch.manual_seed(10)
-    c = mc.AxialAttention_gated_data(32, 32, groups=8, kernel_size=16, stride=1, width=False)
+    ra, sb = mc["AxialAttention_gated_sig"], b.state_dict()
+    assert ra["seed"] == 9
+    assert [k for k, *_ in ra["state"]] == list(sb.keys())
+    for k, *dg in ra["state"]:
+        assert dg == digest(sb[k]), k                      # same registration order -> same RNG stream -> same init
+    assert [tuple(e) for e in ra["params"]] == [(k, p.requires_grad) for k, p in b.named_parameters()]
     torch.manual_seed(10)
     d = model_codes.AxialAttention_gated_data(32, 32, groups=8, kernel_size=16, stride=1, width=False)
-    sc, sd = c.state_dict(), d.state_dict()
-    assert list(sc.keys()) == list(sd.keys())              # fcn1 / fcn2 sit between bn_output and relative, as in the reference
-    for k in sc:
-        assert torch.equal(sc[k], sd[k]), k
+    rc, sd = mc["AxialAttention_gated_data"], d.state_dict()
+    assert rc["seed"] == 10
+    assert [k for k, *_ in rc["state"]] == list(sd.keys())  # fcn1 / fcn2 sit between bn_output and relative, as in the reference
+    for k, *dg in rc["state"]:
+        assert dg == digest(sd[k]), k
     blk = model_codes.AxialBlock_gated_data(32, 16, kernel_size=16)
-    ref_blk = mc.AxialBlock_gated_data(32, 16, kernel_size=16)
-    assert list(blk.state_dict().keys()) == list(ref_blk.state_dict().keys())
+    assert list(blk.state_dict().keys()) == mc["AxialBlock_gated_data_keys"]
