@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MEDT_ABI_VERSION 9
+#define MEDT_ABI_VERSION 10
 
 #define MEDT_OK            0
 #define MEDT_EINVAL       -1   /* bad descriptor / null pointer / size mismatch            */
@@ -345,6 +345,27 @@ int medt_relu_mask(const float* a, const float* y, float* out, size_t n, void* s
  * logits (N,K,HW) float, target (N,HW) int64, counts (N,4) int32 = {tp, fp, fn, tn}; the call zeroes counts itself. */
 int medt_seg_counts(const float* logits, const int64_t* target, int32_t* counts, int N, int K, int HW, float threshold,
                     void* stream);
+
+/* Sliding-window inference on an image larger than the network input (not in the reference, which resizes the dataset
+ * offline; medt_amd/window.py).  The image is cut into T = ny*nx overlapping S x S windows, numbered row-major
+ * (t = iy*nx + ix), window t with its top-left corner at (oy[iy], ox[ix]).  oy (ny) and ox (nx) are int32 DEVICE
+ * arrays, so the launches do not depend on where the windows lie.  ny*nx*channels*S*S and channels*H*W must stay
+ * below 2^31 (MEDT_EUNSUPPORTED above).
+ *
+ * gather: image (C,H,W) -> windows (T,C,S,S); source coordinates are clamped to the image, which is edge replication
+ * where H < S or W < S.
+ *
+ * blend: window logits (T,K,S,S) -> blended (K,H,W) and / or mask (H,W) uint8 {0,255} = blended[1] >= threshold
+ * (test.py:131-137's rule; needs K >= 2); either output may be NULL, not both.  Window pixel (i, j) weighs
+ * w(i) w(j), w(i) = min(i + 1, S - i).  Every output pixel is computed by one work-item that visits the windows
+ * covering it in ascending t and divides sum(w l) by sum(w) once: no atomics, bit-identical from run to run.  A pixel
+ * that ONE window covers receives that window's value unchanged; a pixel that none covers (no plan of
+ * medt_amd.window.plan_windows leaves one) receives 0.  16-byte stores when W % 4 == 0 and the outputs are aligned
+ * (blended to 16 bytes, mask to 4), element stores otherwise. */
+int medt_window_gather(const float* image, float* windows, const int32_t* oy, const int32_t* ox, int C, int H, int W, int S,
+                       int ny, int nx, void* stream);
+int medt_window_blend(const float* win_logits, float* blended, uint8_t* mask, const int32_t* oy, const int32_t* ox, int K,
+                      int H, int W, int S, int ny, int nx, float threshold, void* stream);
 
 #ifdef __cplusplus
 }

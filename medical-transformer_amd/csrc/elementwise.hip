@@ -4,6 +4,7 @@
 //   LoGo patch gather / merge                                (axialnet.py:658-702)
 //   cross-entropy loss                                       (metrics.py:17-20)
 //   Adam with coupled L2 weight decay over a flat buffer     (train.py:111-112,161)
+//   sliding-window gather / blend for images larger than the network input (not in the reference)
 // All HBM-bound: one element per lane, NCHW rows coalesced, per-channel constants via scalar loads.
 #include "medt_kernels.h"
 #include <stdint.h>
@@ -775,6 +776,145 @@ int seg_counts(const float* logits, const int64_t* target, int* counts, int N, i
     const int parts = min(cdiv(HW, MEDT_THREADS), 64);
     hipLaunchKernelGGL(seg_counts_kernel, dim3(parts, N), dim3(MEDT_THREADS), 0, s, logits, target, counts, K, HW, threshold);
     return launch_status("seg_counts");
+}
+
+// --------------------------------------------------------------------------- //
+// Sliding-window inference on images larger than the network input (medt_amd/window.py): cut (C,H,W) into T = ny*nx
+// overlapping S x S windows, and blend the T window logits back into one (K,H,W) map.  Window t = iy*nx + ix has its
+// top-left corner at (oy[iy], ox[ix]); the origins are DEVICE arrays, so one launch geometry serves every plan of an
+// image size.  Both kernels: a work-item is 4 consecutive x of one row, grid-stride loop, 16-byte stores when the
+// destination rows are 16-byte aligned (VEC4), element stores otherwise.
+// --------------------------------------------------------------------------- //
+static inline unsigned grid_strided(size_t items) {
+    return (unsigned)min((items + MEDT_THREADS - 1) / MEDT_THREADS, (size_t)4096);
+}
+
+// windows[t,c,i,j] = image[c, clamp(oy+i), clamp(ox+j)]: clamping to the image is the edge replication of an axis
+// shorter than S (and keeps every read in bounds whatever the origin arrays hold)
+template <bool VEC4>
+__global__ __launch_bounds__(MEDT_THREADS) void window_gather_kernel(const float* __restrict__ image,
+                                                                     float* __restrict__ windows,
+                                                                     const int32_t* __restrict__ oy,
+                                                                     const int32_t* __restrict__ ox, int C, int H, int W,
+                                                                     int S, int nx, size_t items) {
+    const int S4 = (S + 3) >> 2;
+    for (size_t it = (size_t)blockIdx.x * MEDT_THREADS + threadIdx.x; it < items; it += (size_t)gridDim.x * MEDT_THREADS) {
+        const int j0 = (int)(it % S4) * 4;
+        size_t r = it / S4;
+        const int i = (int)(r % S);
+        r /= S;
+        const int c = (int)(r % C), t = (int)(r / C);
+        const int iy = t / nx, ix = t - iy * nx;
+        const int y = min(max(oy[iy] + i, 0), H - 1), x0 = ox[ix] + j0;
+        const float* src = image + ((size_t)c * H + y) * W;
+        float* dst = windows + (((size_t)t * C + c) * S + i) * S + j0;
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = src[min(max(x0 + e, 0), W - 1)];
+        if (VEC4) {
+            *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (j0 + e < S) dst[e] = v[e];
+        }
+    }
+}
+
+int window_gather(const float* image, float* windows, const int32_t* oy, const int32_t* ox, int C, int H, int W, int S,
+                  int ny, int nx, hipStream_t s) {
+    const size_t items = (size_t)ny * nx * C * S * ((S + 3) / 4);
+    if ((S % 4 == 0) && ((uintptr_t)windows % 16 == 0))
+        hipLaunchKernelGGL((window_gather_kernel<true>), dim3(grid_strided(items)), dim3(MEDT_THREADS), 0, s, image, windows,
+                           oy, ox, C, H, W, S, nx, items);
+    else
+        hipLaunchKernelGGL((window_gather_kernel<false>), dim3(grid_strided(items)), dim3(MEDT_THREADS), 0, s, image, windows,
+                           oy, ox, C, H, W, S, nx, items);
+    return launch_status("window_gather");
+}
+
+// blended[k,y,x] = sum_t w_t l_t / sum_t w_t over the windows t that cover (y, x), w_t = w(y - oy) w(x - ox),
+// w(i) = min(i + 1, S - i).  Gather form: the work-item owns its 4 pixels and visits the covering windows in the fixed
+// order iy ascending, ix ascending inside -- no atomics, the same bits on every run.  A pixel covered by ONE window takes
+// that window's value as it is (no (w l) / w round trip).  mask[y,x] = 255 (blended[1,y,x] >= threshold), written by the
+// work-items of k = 1.  The covering rows / columns are located by one pass over oy and one over ox (first and last
+// index whose window reaches the pixel); the test inside the loops makes the result right for any origin arrays.
+template <bool VEC4>
+__global__ __launch_bounds__(MEDT_THREADS) void window_blend_kernel(const float* __restrict__ win, float* __restrict__ blended,
+                                                                    uint8_t* __restrict__ mask,
+                                                                    const int32_t* __restrict__ oy,
+                                                                    const int32_t* __restrict__ ox, int k0, int K,
+                                                                    int H, int W, int S, int ny, int nx, float threshold,
+                                                                    size_t items) {
+    const int W4 = (W + 3) >> 2;
+    for (size_t it = (size_t)blockIdx.x * MEDT_THREADS + threadIdx.x; it < items; it += (size_t)gridDim.x * MEDT_THREADS) {
+        const int x0 = (int)(it % W4) * 4;
+        const size_t r = it / W4;
+        const int y = (int)(r % H), k = k0 + (int)(r / H);
+        int iy_lo = ny, iy_hi = -1, ix_lo = nx, ix_hi = -1;
+        for (int iy = 0; iy < ny; ++iy)
+            if ((unsigned)(y - oy[iy]) < (unsigned)S) { iy_lo = min(iy_lo, iy); iy_hi = iy; }
+        for (int ix = 0; ix < nx; ++ix) {
+            const int d = x0 - ox[ix];                          // the window reaches one of x0 .. x0+3
+            if (d > -4 && d < S) { ix_lo = min(ix_lo, ix); ix_hi = ix; }
+        }
+        float acc[4] = {0.f, 0.f, 0.f, 0.f}, wsum[4] = {0.f, 0.f, 0.f, 0.f}, one[4] = {0.f, 0.f, 0.f, 0.f};
+        int n[4] = {0, 0, 0, 0};
+        for (int iy = iy_lo; iy <= iy_hi; ++iy) {
+            const int i = y - oy[iy];
+            if ((unsigned)i >= (unsigned)S) continue;
+            const float wy = (float)min(i + 1, S - i);
+            for (int ix = ix_lo; ix <= ix_hi; ++ix) {
+                const int d = x0 - ox[ix];
+                if (d <= -4 || d >= S) continue;
+                const float* row = win + ((((size_t)iy * nx + ix) * K + k) * S + i) * S;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int j = d + e;
+                    if ((unsigned)j < (unsigned)S) {
+                        const float l = row[j], w = wy * (float)min(j + 1, S - j);
+                        acc[e] = fmaf(w, l, acc[e]);
+                        wsum[e] += w;
+                        one[e] = l;
+                        ++n[e];
+                    }
+                }
+            }
+        }
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = n[e] == 1 ? one[e] : (n[e] ? acc[e] / wsum[e] : 0.f);
+        const size_t px = (size_t)y * W + x0;
+        if (VEC4) {
+            if (blended) *reinterpret_cast<float4*>(blended + (size_t)k * H * W + px) = make_float4(v[0], v[1], v[2], v[3]);
+            if (mask && k == 1) {
+                uint32_t m = 0;                                   // 4 mask bytes as one 32-bit store (little endian)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) m |= (v[e] >= threshold ? 255u : 0u) << (8 * e);
+                *reinterpret_cast<uint32_t*>(mask + px) = m;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (x0 + e >= W) break;
+                if (blended) blended[(size_t)k * H * W + px + e] = v[e];
+                if (mask && k == 1) mask[px + e] = v[e] >= threshold ? 255 : 0;
+            }
+        }
+    }
+}
+
+int window_blend(const float* win, float* blended, uint8_t* mask, const int32_t* oy, const int32_t* ox, int K, int H, int W,
+                 int S, int ny, int nx, float threshold, hipStream_t s) {
+    const int k0 = blended ? 0 : 1, nk = blended ? K : 1;       // mask only: the foreground channel alone
+    const size_t items = (size_t)nk * H * ((W + 3) / 4);
+    if ((W % 4 == 0) && ((uintptr_t)blended % 16 == 0) && ((uintptr_t)mask % 4 == 0))
+        hipLaunchKernelGGL((window_blend_kernel<true>), dim3(grid_strided(items)), dim3(MEDT_THREADS), 0, s, win, blended, mask,
+                           oy, ox, k0, K, H, W, S, ny, nx, threshold, items);
+    else
+        hipLaunchKernelGGL((window_blend_kernel<false>), dim3(grid_strided(items)), dim3(MEDT_THREADS), 0, s, win, blended,
+                           mask, oy, ox, k0, K, H, W, S, ny, nx, threshold, items);
+    return launch_status("window_blend");
 }
 
 }  // namespace medt

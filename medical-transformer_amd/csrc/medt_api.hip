@@ -905,5 +905,28 @@ int medt_seg_counts(const float* logits, const int64_t* target, int32_t* counts,
     if (!logits || !target || !counts || K < 2 || N < 1 || HW < 1) { set_error("seg_counts: bad arguments"); return MEDT_EINVAL; }
     return seg_counts(logits, target, counts, N, K, HW, threshold, (hipStream_t)stream);
 }
+int medt_window_gather(const float* image, float* windows, const int32_t* oy, const int32_t* ox, int C, int H, int W, int S,
+                       int ny, int nx, void* stream) {
+    if (!image || !windows || !oy || !ox || C < 1 || H < 1 || W < 1 || S < 1 || ny < 1 || nx < 1) {
+        set_error("window_gather: bad arguments"); return MEDT_EINVAL;
+    }
+    if ((double)ny * nx * C * S * S >= 2147483648.0 || (double)C * H * W >= 2147483648.0) {
+        set_error("window_gather: %d x %d windows of %d x %d x %d (image %d x %d): 2^31 elements or more", ny, nx, C, S, S, H, W);
+        return MEDT_EUNSUPPORTED;
+    }
+    return window_gather(image, windows, oy, ox, C, H, W, S, ny, nx, (hipStream_t)stream);
+}
+int medt_window_blend(const float* win_logits, float* blended, uint8_t* mask, const int32_t* oy, const int32_t* ox, int K,
+                      int H, int W, int S, int ny, int nx, float threshold, void* stream) {
+    if (!win_logits || (!blended && !mask) || !oy || !ox || K < 1 || (mask && K < 2) || H < 1 || W < 1 || S < 1 || ny < 1 ||
+        nx < 1) {
+        set_error("window_blend: bad arguments"); return MEDT_EINVAL;
+    }
+    if ((double)ny * nx * K * S * S >= 2147483648.0 || (double)K * H * W >= 2147483648.0) {
+        set_error("window_blend: %d x %d windows of %d x %d x %d (image %d x %d): 2^31 elements or more", ny, nx, K, S, S, H, W);
+        return MEDT_EUNSUPPORTED;
+    }
+    return window_blend(win_logits, blended, mask, oy, ox, K, H, W, S, ny, nx, threshold, (hipStream_t)stream);
+}
 
 }  // extern "C"

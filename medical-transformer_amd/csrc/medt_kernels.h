@@ -118,6 +118,10 @@ int relu_fwd(const float* x, float* y, size_t total, hipStream_t s);
 int up2x_relu_add_fwd(const float* x, const float* skip, float* y, int NC, int H, int W, hipStream_t s);
 int up2x_relu_bwd(const float* x, const float* dy, float* dx, int NC, int H, int W, hipStream_t s);
 int patch_gather(const float* x, float* xp, int N, int C, int S, int P, int G, hipStream_t s);
+int window_gather(const float* image, float* windows, const int32_t* oy, const int32_t* ox, int C, int H, int W, int S,
+                  int ny, int nx, hipStream_t s);
+int window_blend(const float* win, float* blended, uint8_t* mask, const int32_t* oy, const int32_t* ox, int K, int H, int W,
+                 int S, int ny, int nx, float threshold, hipStream_t s);
 int logo_merge_fwd(const float* x, const float* yp, float* y, int N, int C, int S, int P, int G, hipStream_t s);
 int logo_merge_bwd(const float* dy, float* dx, float* dyp, int N, int C, int S, int P, int G, hipStream_t s);
 int ce_parts(size_t npix);

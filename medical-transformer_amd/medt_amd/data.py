@@ -170,12 +170,14 @@ class MetricList:
 
 
 def make_synthetic_dataset(root, n=16, size=128, seed=3000, gray=False):
-    """BASELINE.json config 1 plumbing data: n PNG pairs img/NNNN.png (uniform uint8) + labelcol/NNNN.png (0/255)."""
+    """BASELINE.json config 1 plumbing data: n PNG pairs img/NNNN.png (uniform uint8) + labelcol/NNNN.png (0/255).
+    size: the side of square images, or (height, width)."""
     rng = np.random.RandomState(seed)
     chk_mkdir(os.path.join(root, "img"), os.path.join(root, "labelcol"))
+    h, w = (size, size) if isinstance(size, int) else size
     for k in range(n):
-        img = rng.randint(0, 256, (size, size) if gray else (size, size, 3)).astype(np.uint8)
-        lab = (rng.rand(size, size) < 0.5).astype(np.uint8) * 255
+        img = rng.randint(0, 256, (h, w) if gray else (h, w, 3)).astype(np.uint8)
+        lab = (rng.rand(h, w) < 0.5).astype(np.uint8) * 255
         Image.fromarray(img).save(os.path.join(root, "img", f"{k:04d}.png"))
         Image.fromarray(lab).save(os.path.join(root, "labelcol", f"{k:04d}.png"))
     return root

@@ -419,3 +419,54 @@ def seg_counts(logits, target, threshold=0.5):
     L.check(L.lib().medt_seg_counts(logits.data_ptr(), target.data_ptr(), counts.data_ptr(), N, K, HW, float(threshold),
                                     _stream()), "medt_seg_counts")
     return counts
+
+
+# --------------------------------------------------------------------------- #
+# sliding windows over an image larger than the network input (medt_amd.window)
+# --------------------------------------------------------------------------- #
+def _window_origins(oy, ox, like):
+    for o in (oy, ox):
+        if o.dtype != torch.int32 or o.dim() != 1 or o.numel() < 1 or o.device != like.device:
+            raise L.MedtError("window origins: non-empty 1-D int32 tensors on the image's device expected")
+    return oy.contiguous(), ox.contiguous()
+
+
+def window_gather(image, oy, ox, S, out=None):
+    """(C,H,W) image -> (len(oy)*len(ox), C, S, S) windows, row-major, window (iy, ix) cut at (oy[iy], ox[ix]) with the
+    source coordinates clamped to the image.  oy / ox: int32 device tensors.  `out`: a contiguous float32 buffer whose
+    first T windows are written (WindowInfer keeps the padding of its last batch behind them)."""
+    _require_device(image)
+    if image.dim() != 3 or image.dtype != torch.float32:
+        raise L.MedtError("window_gather: a float32 (C,H,W) image expected")
+    image = image.contiguous()
+    oy, ox = _window_origins(oy, ox, image)
+    Cc, H, W = image.shape
+    T = oy.numel() * ox.numel()
+    if out is None:
+        out = torch.empty((T, Cc, S, S), device=image.device, dtype=torch.float32)
+    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.device != image.device or out.dim() != 4
+          or out.shape[0] < T or tuple(out.shape[1:]) != (Cc, S, S)):
+        raise L.MedtError("window_gather: out must be a contiguous float32 (>=T,C,S,S) tensor on the image's device")
+    L.check(L.lib().medt_window_gather(image.data_ptr(), out.data_ptr(), oy.data_ptr(), ox.data_ptr(), Cc, H, W, S,
+                                       oy.numel(), ox.numel(), _stream()), "medt_window_gather")
+    return out[:T]
+
+
+def window_blend(win_logits, oy, ox, H, W, threshold=0.5, want_logits=True, want_mask=True):
+    """(T,K,S,S) window logits -> (blended (K,H,W) float32 or None, mask (H,W) uint8 {0,255} or None): the weighted mean of
+    the windows covering each pixel (weight min(i+1, S-i) per axis), mask = blended[1] >= threshold."""
+    _require_device(win_logits)
+    if win_logits.dim() != 4 or win_logits.shape[2] != win_logits.shape[3] or win_logits.dtype != torch.float32:
+        raise L.MedtError("window_blend: float32 (T,K,S,S) window logits expected")
+    if not (want_logits or want_mask):
+        raise L.MedtError("window_blend: nothing asked for")
+    win_logits = win_logits.contiguous()
+    oy, ox = _window_origins(oy, ox, win_logits)
+    T, K, S, _ = win_logits.shape
+    if T != oy.numel() * ox.numel():
+        raise L.MedtError(f"window_blend: {T} windows for a plan of {oy.numel()} x {ox.numel()}")
+    blended = torch.empty((K, H, W), device=win_logits.device, dtype=torch.float32) if want_logits else None
+    mask = torch.empty((H, W), device=win_logits.device, dtype=torch.uint8) if want_mask else None
+    L.check(L.lib().medt_window_blend(win_logits.data_ptr(), L.ptr(blended), L.ptr(mask), oy.data_ptr(), ox.data_ptr(), K,
+                                      H, W, S, oy.numel(), ox.numel(), float(threshold), _stream()), "medt_window_blend")
+    return blended, mask

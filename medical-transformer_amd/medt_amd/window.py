@@ -1,0 +1,106 @@
+"""Sliding-window inference for images larger than the network input (not in the reference, which resizes its datasets
+offline to the one img_size a network is built for: the relative-position tables are (2 gp, 2L-1) with L fixed at
+construction, and MedT's local branch cuts exactly 4x4 patches of img_size/4).
+
+An (C,H,W) image is cut on the device into overlapping S x S windows (ops.window_gather), the windows run through ONE
+InferStep `gather` at a time, and the window logits are blended back into one (K,H,W) map and its thresholded mask
+(ops.window_blend) -- no host round trip per window.
+
+Plan, per axis of length D:  n = 1 if D <= S else ceil((D - S) / stride) + 1 windows at o_i = min(i stride, max(D, S) - S):
+the last window sits flush with the far edge and none starts outside the image.  An axis shorter than S gets one window
+whose missing rows / columns replicate the edge; the prediction is cropped back to D.  Windows are numbered row-major,
+t = iy len(ox) + ix, which is also the order the blend sums in.
+
+Blend: window pixel (i, j) weighs w(i) w(j), w(i) = min(i + 1, S - i) -- integers, so weights and weight sums are exact
+in float32 and never zero.  A pixel that one window covers takes that window's logit unchanged, so an S x S image
+reproduces InferStep bit for bit."""
+from __future__ import annotations
+
+import torch
+
+from . import _lib as L
+from . import ops
+from .trainer import InferStep
+
+
+def _axis_origins(D: int, S: int, stride: int):
+    n = 1 if D <= S else -(-(D - S) // stride) + 1
+    return [min(i * stride, max(D, S) - S) for i in range(n)]
+
+
+def plan_windows(H: int, W: int, S: int, stride: int = None):
+    """-> (oy, ox): the window origins along y and along x (lists of int, ascending)."""
+    if stride is None:
+        stride = max(1, S // 2)
+    if H < 1 or W < 1 or S < 1 or not 1 <= stride <= S:
+        raise ValueError(f"plan_windows: need H, W, S >= 1 and 1 <= stride <= S (got H={H} W={W} S={S} stride={stride})")
+    return _axis_origins(H, S, stride), _axis_origins(W, S, stride)
+
+
+def blend_weight(S: int):
+    """w(i) = min(i + 1, S - i), i = 0 .. S-1."""
+    return [min(i + 1, S - i) for i in range(S)]
+
+
+class WindowInfer:
+    """Eval-mode inference of `model` (built for size x size inputs) on images of any H x W.
+
+    infer = WindowInfer(model, size); blended, mask = infer(image)            image (C,H,W) or (1,C,H,W) on the device
+                                      blended, mask, counts = infer(image, target)      target (H,W) / (1,H,W) int64
+    blended (K,H,W) float32 logits, mask (H,W) uint8 {0,255} = blended[1] >= threshold (what test.py writes),
+    counts (1,4) int32 {tp, fp, fn, tn} of the mask against target > 0 (ops.seg_counts).  The outputs are fresh tensors.
+
+    The T windows run `gather` per forward replay; the last, shorter batch is padded with copies of its last window and
+    the padding's logits are dropped (test.py's rule for its last batch).  In eval mode the windows of a batch do not
+    interact; in train mode they would (batch statistics), so a model in train mode is refused."""
+
+    def __init__(self, model, size: int, gather: int = 4, stride: int = None, threshold: float = 0.5, use_graph: bool = True):
+        self.model, self.size, self.gather, self.threshold = model, int(size), max(1, int(gather)), float(threshold)
+        self.stride = max(1, self.size // 2) if stride is None else int(stride)
+        if not 1 <= self.stride <= self.size:
+            raise L.MedtError(f"WindowInfer: 1 <= stride <= size expected (stride {self.stride}, size {self.size})")
+        self.infer = InferStep(model, use_graph=use_graph, threshold=threshold)
+        self._plans = {}
+
+    def _plan(self, H, W, device):
+        key = (H, W, str(device))
+        plan = self._plans.get(key)
+        if plan is None:
+            if len(self._plans) >= 64:
+                self._plans.clear()
+            oy, ox = plan_windows(H, W, self.size, self.stride)
+            plan = self._plans[key] = (torch.tensor(oy, dtype=torch.int32, device=device),
+                                       torch.tensor(ox, dtype=torch.int32, device=device))
+        return plan
+
+    def __call__(self, image, target=None):
+        if self.model.training:
+            raise L.MedtError("WindowInfer: the model is in train mode -- batch statistics would make the windows of a "
+                              "batch depend on each other; call model.eval() first")
+        ops._require_device(image)
+        if image.dim() == 4 and image.shape[0] == 1:
+            image = image[0]
+        if image.dim() != 3:
+            raise L.MedtError("WindowInfer: one (C,H,W) or (1,C,H,W) image expected")
+        image = image.contiguous()
+        Cc, H, W = image.shape
+        S, g = self.size, self.gather
+        oy, ox = self._plan(H, W, image.device)
+        T = oy.numel() * ox.numel()
+        Tpad = -(-T // g) * g
+        windows = torch.empty((Tpad, Cc, S, S), device=image.device, dtype=torch.float32)
+        ops.window_gather(image, oy, ox, S, out=windows)
+        if Tpad > T:
+            windows[T:] = windows[T - 1]
+        logits = None
+        for b in range(0, T, g):
+            out = self.infer(windows[b:b + g])
+            if logits is None:
+                logits = torch.empty((T,) + tuple(out.shape[1:]), device=image.device, dtype=torch.float32)
+            n = min(g, T - b)
+            logits[b:b + n].copy_(out[:n])         # the replay's outputs are static: the next replay overwrites them
+        blended, mask = ops.window_blend(logits, oy, ox, H, W, self.threshold)
+        if target is None:
+            return blended, mask
+        counts = ops.seg_counts(blended.unsqueeze(0), target.reshape(1, H, W), self.threshold)
+        return blended, mask, counts
