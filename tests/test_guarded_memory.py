@@ -1,0 +1,154 @@
+"""Global memory of the kernels, checked by the MMU: the product's Python path on the CPU lane emulator with every buffer that
+reaches the C ABI in a guard-page arena at its logical size (tests/guarded_mem.py), family by family in child processes
+(tests/guard_driver.py), once with the buffers ending on a guard page ("tail": overruns fault) and once starting behind one
+("head": underruns fault).  Exact guarding cannot misalign a tensor whose byte count is a multiple of 16, so the scalar bodies
+behind the kernels' alignment guards get a family of their own on offset pointers (test_scalar_bodies_behind_the_alignment_guards).  A return code of -11 means
+a kernel read or wrote outside a buffer it was given; the report names the last entry point and case announced.
+
+CPU only.  MEDT_GUARD_FULL=1 adds the largest shapes of each family and the MedT-128 training step (README.md)."""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import guard_driver as D
+import guarded_mem as G
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DRIVER = os.path.join(ROOT, "tests", "guard_driver.py")
+FULL = os.environ.get("MEDT_GUARD_FULL") == "1"
+FAMILIES = ["attention", "attention_random", "attention_repair", "conv", "recorded", "small_ops", "blocks", "train"]
+if FULL:
+    FAMILIES.append("train_medt128")                      # MedT at 128 px, N = 4: minutes per placement
+# families whose tail placement must have run calls with a pointer that is not 16-byte aligned.  What this count shows is
+# small: the pointers concerned are 4-byte gate scalars, num_batches_tracked, odd-sized tables, biases and statistics blocks and
+# tensors of ragged shapes -- NOT the tensors the kernels' alignment guards inspect when their shape condition holds (those have
+# byte counts that are multiples of 16 and are aligned in both exact placements).  The guards' pointer clauses are exercised by
+# test_scalar_bodies_behind_the_alignment_guards.
+MUST_MISALIGN = {"attention", "attention_random", "conv", "recorded", "small_ops"}
+
+
+@pytest.mark.parametrize("placement", G.PLACEMENTS)
+@pytest.mark.parametrize("nbytes", [1, 4, G.PAGE - 4, G.PAGE, 3 * G.PAGE + 12])
+def test_arena_is_armed(nbytes, placement):
+    """Both neighbouring pages of an allocation have no permissions (/proc/self/maps; nothing is made to fault), the buffer
+    sits flush against the guard page its placement names, and the registry knows exactly its bytes."""
+    arena = G.Arena(placement, check_maps=False)
+    npages = -(-nbytes // G.PAGE)
+    m, base, off, got_pages = arena._map(nbytes)
+    assert got_pages == npages and len(m) == (npages + 2) * G.PAGE
+    assert G.Arena.guards_armed(base, npages)
+    with open("/proc/self/maps") as f:
+        maps = f.read()
+    assert G._perms_at(maps, base) == "---p" and G._perms_at(maps, base + (npages + 1) * G.PAGE) == "---p"
+    assert G._perms_at(maps, base + G.PAGE) == "rw-p" and G._perms_at(maps, base + npages * G.PAGE) == "rw-p"
+    start = base + off
+    if placement == "tail":
+        assert start + nbytes == base + (npages + 1) * G.PAGE            # the last byte is the last byte before the guard page
+    else:
+        assert start == base + G.PAGE                                      # the first byte is the first byte behind it
+    assert arena.owner(start, nbytes) == (start, nbytes)
+    assert arena.owner(start - 1) is None and arena.owner(start + nbytes) is None and arena.owner(start, nbytes + 1) is None
+    arena.release()
+
+
+@pytest.mark.parametrize("placement", G.PLACEMENTS)
+def test_arena_tensors(placement):
+    arena = G.Arena(placement)
+    t = arena.tensor((3, 5), torch.float32)
+    assert t.shape == (3, 5) and torch.isnan(t).all()                     # the stand-in for torch.empty: quiet NaNs ...
+    assert torch.isnan(arena.tensor((7,), torch.bfloat16).float()).all() and torch.isnan(arena.tensor((2,), torch.float64)).all()
+    assert (arena.tensor((9,), torch.uint8) == 0x7F).all() and (arena.tensor((3,), torch.int32) == 0x7F7F7F7F).all()   # ... 0x7f bytes
+    assert (arena.tensor((4, 4), torch.float32, "zeros") == 0).all()
+    e = arena.tensor((0, 3), torch.float32)
+    assert e.shape == (0, 3) and e.numel() == 0
+    a = arena.numpy((5,), "float32")
+    assert a.ctypes.data % 4 == 0 and arena.owner(a.ctypes.data, 20) is not None
+    src = torch.arange(10.0).reshape(2, 5)
+    c = arena.copy_of(src)
+    assert torch.equal(c, src) and arena.owner(c.data_ptr(), 40) == (c.data_ptr(), 40)
+    if placement == "tail":
+        assert (c.data_ptr() + 40) % G.PAGE == 0 and c.data_ptr() % 16 == 8
+    else:
+        assert c.data_ptr() % G.PAGE == 0
+    ns = G.guarded_torch(arena)
+    for t in (ns.empty((2, 3), dtype=torch.float32, device="cpu"), ns.zeros(5, device="cpu", dtype=torch.float32), ns.empty_like(src),
+              ns.zeros_like(src), ns.ones(3), ns.full((2,), 1.5), ns.tensor([1, 2, 3], dtype=torch.int32)):
+        assert arena.owner(t.data_ptr(), t.numel() * t.element_size()) is not None
+    assert ns.ones(3).tolist() == [1, 1, 1] and ns.full((2,), 1.5).tolist() == [1.5, 1.5] and ns.zeros(5).sum() == 0
+    arena.release()
+
+
+def run_family(family, placement, timeout=7000):
+    env = dict(os.environ, **D.FAMILY_ENV.get(family, {}))
+    r = subprocess.run([sys.executable, DRIVER, family, placement], env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+    lines = r.stdout.strip().splitlines()
+    last_call = next((ln for ln in reversed(lines) if ln.startswith("CALL ")), "(no library call announced)")
+    report = "guard_driver %s %s: return code %d%s\nlast announced: %s\n%s" % (
+        family, placement, r.returncode, " (SIGSEGV: a kernel left a buffer it was given)" if r.returncode == -11 else "", last_call,
+        r.stderr[-4000:])
+    assert r.returncode == 0, report
+    return json.loads(lines[-1])
+
+
+@pytest.mark.parametrize("placement", G.PLACEMENTS)
+@pytest.mark.parametrize("family", FAMILIES)
+def test_family_on_guarded_memory(family, placement):
+    s = run_family(family, placement)
+    print(json.dumps(s))
+    assert s["cases"] > 0 and s["calls"] > 0 and s["pointers"] > 0
+    assert s["unguarded"] == 0 and s["allowed"] == 0, s                   # a condition, not a measurement
+    assert s["in_arena"] + s["stood_in"] == s["pointers"], s
+    if placement == "tail" and family in MUST_MISALIGN:
+        assert s["misaligned_calls"] > 0, s
+
+
+def test_scalar_bodies_behind_the_alignment_guards():
+    """axial_fast.hip (four-rows forward), conv_mfma.hip (conv_wgrad_v4_ok), elementwise.hip (bn_fin_apply, up2x_relu_add_fwd) and
+    medt_api.hip (conv_block_bwd) pick a 16-byte body when a shape condition holds AND the tensors are 16-byte aligned.  Shapes
+    that pass the shape condition, every tensor at 12 (mod 16) with a canary element behind it (arena placement "offset"): the
+    pointer clause alone sends them to the scalar bodies, whose results are held to the same references as everywhere else.
+    Asserted: each pointer those guards inspect was seen misaligned, and no canary was written."""
+    s = run_family("offset_pointers", "offset")
+    seen = s["misaligned_pointers"]
+    for guard, pointers in D.GUARD_POINTERS.items():
+        for ptr in pointers:
+            assert seen.get(ptr, 0) > 0, (guard, ptr, sorted(seen))
+    assert s["unguarded"] == 0 and s["allowed"] == 0 and s["canaries"] > 0, s
+
+
+def test_offset_placement_and_its_canary():
+    arena = G.Arena("offset")
+    t = arena.tensor((64,), torch.float32)
+    assert t.data_ptr() % 16 == 12 and (t.data_ptr() + 64 * 4 + 4) % G.PAGE == 0          # 4 canary bytes, then the guard page
+    assert arena.owner(t.data_ptr(), 256) == (t.data_ptr(), 256) and arena.owner(t.data_ptr() + 256) is None
+    assert arena.check_canaries() == 1
+    import ctypes
+    ctypes.memset(t.data_ptr() + 256, 0, 4)                                                # "one element past the end"
+    with pytest.raises(AssertionError):
+        arena.check_canaries()
+    arena.release()
+
+
+def test_handle_convention_matches_the_header():
+    """The proxy skips, as no device buffers, the last void* of every entry point (the stream) and every argument of the
+    medt_queue_* functions (queue handles and streams).  include/medt_abi.h must say the same, for every symbol bound."""
+    import re
+    from medt_amd import _lib as L
+    import ctypes as C
+    with open(os.path.join(ROOT, "include", "medt_abi.h")) as f:
+        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
+    protos = {m.group(1): [a.strip() for a in m.group(2).split(",")] for m in re.finditer(r"\b(medt_\w+)\s*\(([^;{}]*?)\)\s*;", text)}
+    for name, (_, argtypes) in L.SIGNATURES.items():
+        assert name in protos, name
+        params = [] if protos[name] in ([""], ["void"]) else protos[name]
+        assert len(params) == len(argtypes), (name, params)
+        if name.startswith("medt_queue_"):
+            for prm in params:
+                assert re.fullmatch(r"(const\s+)?void\s*\*\s*(queue|stream|aux_stream)", prm), (name, prm)
+        elif C.c_void_p in argtypes:
+            assert argtypes[-1] is C.c_void_p and re.fullmatch(r"void\s*\*\s*stream", params[-1]), (name, params[-1])
+            assert not any(re.search(r"\bstream\b", prm) for prm in params[:-1]), (name, params)
