@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MEDT_ABI_VERSION 10
+#define MEDT_ABI_VERSION 11
 
 #define MEDT_OK            0
 #define MEDT_EINVAL       -1   /* bad descriptor / null pointer / size mismatch            */
@@ -330,6 +330,30 @@ int medt_ce_fwd(const float* logits, const int64_t* target, float* partials, flo
                 int ignore_index, void* stream);
 int medt_ce_bwd(const float* logits, const int64_t* target, const float* loss_out, const float* dloss, float* dlogits,
                 int N, int K, int HW, int ignore_index, void* stream);
+
+/* Segmentation loss = ce_scale * CE + dice_scale * Dice (either scale may be 0: that term is then left out).
+ *   p = softmax over the K classes; a pixel is VALID when its target is not ignore_index and lies in [0, K).
+ *   CE   = sum_valid w[t_i] (-log p_i,t_i) / sum_valid w[t_i]      F.cross_entropy(weight=w, reduction='mean'), what the
+ *          reference's LogNLLLoss(weight=...) computes (metrics.py:17-20); class_weight NULL: w = 1 (medt_ce_fwd's value);
+ *          a zero denominator gives NaN, as in torch.
+ *   Dice = 1 - mean over images n and classes k of (2 I_nk + eps) / (P_nk + T_nk + eps), with I_nk = sum p_ik [t_i = k],
+ *          P_nk = sum p_ik, T_nk = sum [t_i = k] over the valid pixels of image n ONLY (per image, not per batch: with equal
+ *          shards the mean of the ranks' gradients is the gradient of the global batch).  Needs 2 <= K <= 8; the weighted
+ *          cross entropy alone (dice_scale == 0) takes any K >= 1.  eps >= 0.
+ * logits (N,K,HW) float, target (N,HW) int64, class_weight K floats or NULL.
+ * out: medt_seg_loss_out_floats() floats = [loss, sum of counted weights (the pixel count when class_weight is NULL),
+ * number of targets outside [0,K) that are not ignore_index (excluded and counted, as medt_ce_fwd does), CE, Dice] followed
+ * by the 2*N*K per-(image, class) coefficients of dDice/dp the backward reads (written when dice_scale != 0).
+ * partials: medt_seg_loss_workspace() floats.  fwd is two launches, bwd one (recomputes the softmax; dloss: one device float
+ * or NULL = 1; writes all K channels of dlogits, exactly 0 at pixels that are not valid).  No float atomics: every sum has
+ * a fixed order, so results are bit-identical from run to run.  bwd must be given the scales, eps and class_weight of fwd. */
+size_t medt_seg_loss_workspace(int N, int K, int HW);
+size_t medt_seg_loss_out_floats(int N, int K);
+int medt_seg_loss_fwd(const float* logits, const int64_t* target, const float* class_weight, float* partials, float* out,
+                      int N, int K, int HW, int ignore_index, float ce_scale, float dice_scale, float eps, void* stream);
+int medt_seg_loss_bwd(const float* logits, const int64_t* target, const float* class_weight, const float* out,
+                      const float* dloss, float* dlogits, int N, int K, int HW, int ignore_index, float ce_scale,
+                      float dice_scale, float eps, void* stream);
 
 /* torch.optim.Adam(lr, betas, eps, weight_decay) over one flat buffer (train.py:111-112,161).
  * state: 3 device floats [step, 1-b1^step, 1-b2^step], zero-initialised; advanced on the device so a captured

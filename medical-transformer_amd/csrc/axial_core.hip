@@ -550,13 +550,20 @@ __global__ __launch_bounds__(MEDT_THREADS) void attn_bwd_kernel(
     const float e_qk = b_qk * MEDT_LOG2E, e_qr = b_qr * MEDT_LOG2E, e_kr = b_kr * MEDT_LOG2E;
     const int ls = threadIdx.x / L, idx = threadIdx.x - ls * L;
     const bool active = ls < t.nseq;
-    // Wrapped-diagonal second pass (no LDS float atomics in the inner loop, which run ~1 lane/clk on gfx950):
+    // Wrapped-diagonal second pass (no LDS float atomics at all -- in the inner loop they run ~1 lane/clk on gfx950, and the
+    // hand-over of the table sums behind the barrier below has a fixed order, so this form is bit-reproducible):
     // needs the L lanes of a sequence inside one wave so column accumulators can rotate between lanes.
     const bool diag = POS && L <= 64 && (L & (L - 1)) == 0;
     float dqkv_v[NCH];
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) dqkv_v[ch] = 0.f;
     float gacc[4] = {0.f, 0.f, 0.f, 0.f};       // f_qr, f_kr, f_sve, f_sv
+    // relative-table gradients of the wrapped-diagonal sweep, lane-private until the fixed-order hand-over behind the barrier
+    float aq_hi[HQ], aq_lo[HQ], ak_hi[HQ], ak_lo[HQ], av_hi[GP], av_lo[GP];
+#pragma unroll
+    for (int c = 0; c < HQ; ++c) aq_hi[c] = aq_lo[c] = ak_hi[c] = ak_lo[c] = 0.f;
+#pragma unroll
+    for (int c = 0; c < GP; ++c) av_hi[c] = av_lo[c] = 0.f;
     if (active) {
         const float* qp = S.reg + ls * S.RS;
         const float* kp = qp + HQ * L;
@@ -639,20 +646,17 @@ __global__ __launch_bounds__(MEDT_THREADS) void attn_bwd_kernel(
             const int d_hi = dl + L - 1, d_lo = dl > 0 ? dl - 1 : 0;
             const int src_lane = (threadIdx.x & 63 & ~Lm) | ((dl - 1) & Lm);
             float tq_hi[HQ], tq_lo[HQ], tk_hi[HQ], tk_lo[HQ], tv_hi[GP], tv_lo[GP];
-            float aq_hi[HQ], aq_lo[HQ], ak_hi[HQ], ak_lo[HQ], av_hi[GP], av_lo[GP];
             float dk[HQ], dv[GP], dq_d[HQ];
 #pragma unroll
             for (int c = 0; c < HQ; ++c) {
                 dq_d[c] = 0.f;
                 tq_hi[c] = S.tq[c * TL + d_hi]; tq_lo[c] = S.tq[c * TL + d_lo];
                 tk_hi[c] = S.tk[c * TL + d_hi]; tk_lo[c] = S.tk[c * TL + d_lo];
-                aq_hi[c] = aq_lo[c] = ak_hi[c] = ak_lo[c] = 0.f;
                 dk[c] = 0.f;
             }
 #pragma unroll
             for (int c = 0; c < GP; ++c) {
                 tv_hi[c] = S.tv[c * TL + d_hi]; tv_lo[c] = S.tv[c * TL + d_lo];
-                av_hi[c] = av_lo[c] = 0.f;
                 dv[c] = 0.f;
             }
 #pragma unroll 2
@@ -724,20 +728,6 @@ __global__ __launch_bounds__(MEDT_THREADS) void attn_bwd_kernel(
             for (int c = 0; c < HQ; ++c) dqkv_v[HQ + c] = __shfl(dk[c], owner, 64);
 #pragma unroll
             for (int c = 0; c < GP; ++c) dqkv_v[GP + c] = __shfl(dv[c], owner, 64);
-#pragma unroll
-            for (int c = 0; c < HQ; ++c) {
-                atomicAdd(&S.dtq[c * TL + d_hi], aq_hi[c]);
-                atomicAdd(&S.dtk[c * TL + d_hi], ak_hi[c]);
-                if (dl > 0) {
-                    atomicAdd(&S.dtq[c * TL + d_lo], aq_lo[c]);
-                    atomicAdd(&S.dtk[c * TL + d_lo], ak_lo[c]);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < GP; ++c) {
-                atomicAdd(&S.dtv[c * TL + d_hi], av_hi[c]);
-                if (dl > 0) atomicAdd(&S.dtv[c * TL + d_lo], av_lo[c]);
-            }
         } else
         // ---------------- column-oriented: thread owns key column j = idx ----------------
         {
@@ -788,6 +778,44 @@ __global__ __launch_bounds__(MEDT_THREADS) void attn_bwd_kernel(
         }
     }
     __syncthreads();                                    // all reads of reg / tables / atomics done
+    if (diag) {
+        // Table gradients of the wrapped-diagonal sweep, in a FIXED order (no float atomics: the same bits on every run).  Lane
+        // delta of a sequence holds the sums for the entries d_hi = delta + L - 1 and d_lo = delta - 1, which no other lane of
+        // that sequence touches.  First the sequences of a wave: a butterfly over the lane bits above L (lanes of sequences
+        // beyond the tile carry zeros).  Then the waves take turns, in wave order, with plain read-modify-writes.
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        for (int o = L; o < 64; o <<= 1) {
+#pragma unroll
+            for (int c = 0; c < HQ; ++c) {
+                aq_hi[c] += __shfl_xor(aq_hi[c], o, 64); aq_lo[c] += __shfl_xor(aq_lo[c], o, 64);
+                ak_hi[c] += __shfl_xor(ak_hi[c], o, 64); ak_lo[c] += __shfl_xor(ak_lo[c], o, 64);
+            }
+#pragma unroll
+            for (int c = 0; c < GP; ++c) {
+                av_hi[c] += __shfl_xor(av_hi[c], o, 64); av_lo[c] += __shfl_xor(av_lo[c], o, 64);
+            }
+        }
+        const int d_hi = lane + L - 1, d_lo = lane - 1;
+        for (int w = 0; w < MEDT_WAVES; ++w) {
+            if (wave == w && lane < L) {
+#pragma unroll
+                for (int c = 0; c < HQ; ++c) {
+                    S.dtq[c * TL + d_hi] += aq_hi[c];
+                    S.dtk[c * TL + d_hi] += ak_hi[c];
+                    if (lane > 0) {
+                        S.dtq[c * TL + d_lo] += aq_lo[c];
+                        S.dtk[c * TL + d_lo] += ak_lo[c];
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < GP; ++c) {
+                    S.dtv[c * TL + d_hi] += av_hi[c];
+                    if (lane > 0) S.dtv[c * TL + d_lo] += av_lo[c];
+                }
+            }
+            __syncthreads();
+        }
+    }
     if (active) {
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) S.reg[ls * S.RS + ch * L + idx] = dqkv_v[ch];

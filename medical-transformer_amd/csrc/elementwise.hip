@@ -527,6 +527,238 @@ int ce_bwd(const float* logits, const int64_t* target, const float* loss_out, co
 }
 
 // --------------------------------------------------------------------------- //
+// segmentation loss = ce_scale * class-weighted cross entropy + dice_scale * soft Dice (per image, per class)
+//   three launches like the plain cross entropy above: partial sums per workgroup, one finalize, one pointwise backward.
+//   KD = 0: cross entropy only, any K (run-time class loop).  KD = K in [2, 8]: Dice on, the per-class sums live in registers.
+//   The grid runs over (image, block of 256 pixels of that image): a workgroup never straddles two images, so the Dice
+//   sums of an image are the sums of its own bpi = ceil(HW / 256) partial rows and the backward's per-image coefficients are
+//   workgroup-uniform.  No float atomics anywhere: every sum has a fixed order (block_sum, then double in the finalize).
+// --------------------------------------------------------------------------- //
+// partials [N][bpi][3 + 3 KD] = {sum w nll, sum w, targets outside [0,K) that are not `ignore`, I_k.., P_k.., T_k..}
+template <int KD>
+__global__ __launch_bounds__(MEDT_THREADS) void seg_loss_fwd_kernel(const float* __restrict__ logits,
+                                                                    const int64_t* __restrict__ target,
+                                                                    const float* __restrict__ weight,
+                                                                    float* __restrict__ partials, int K, int HW, int bpi,
+                                                                    int ignore) {
+    constexpr int NV = 3 + 3 * KD;
+    MEDT_STATIC_SHARED float red[MEDT_WAVES * NV];
+    const int n = blockIdx.x / bpi;
+    const int p = (blockIdx.x - n * bpi) * MEDT_THREADS + threadIdx.x;       // pixel within image n
+    float v[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = 0.f;
+    if (p < HW) {
+        const int64_t t = target[(size_t)n * HW + p];
+        const bool valid = t != ignore && t >= 0 && t < K;
+        if (t != ignore && !valid) v[2] = 1.f;                 // F.cross_entropy raises on these: counted, reported
+        if (valid) {
+            const float* lp = logits + (size_t)n * K * HW + p;
+            const float w = weight ? weight[t] : 1.f;
+            if constexpr (KD == 0) {
+                float m = lp[0];
+                for (int k = 1; k < K; ++k) m = fmaxf(m, lp[(size_t)k * HW]);
+                float sum = 0.f;
+                for (int k = 0; k < K; ++k) sum += __expf(lp[(size_t)k * HW] - m);
+                v[0] = w * (m + __logf(sum) - lp[(size_t)t * HW]);
+            } else {
+                float l[KD];
+#pragma unroll
+                for (int k = 0; k < KD; ++k) l[k] = lp[(size_t)k * HW];
+                float m = l[0], lt = l[0];
+#pragma unroll
+                for (int k = 1; k < KD; ++k) { m = fmaxf(m, l[k]); lt = (k == t) ? l[k] : lt; }
+                float sum = 0.f;
+#pragma unroll
+                for (int k = 0; k < KD; ++k) { l[k] = __expf(l[k] - m); sum += l[k]; }
+                v[0] = w * (m + __logf(sum) - lt);
+                const float inv = 1.f / sum;
+#pragma unroll
+                for (int k = 0; k < KD; ++k) {
+                    const float pk = l[k] * inv;
+                    v[3 + k] = (k == t) ? pk : 0.f;
+                    v[3 + KD + k] = pk;
+                    v[3 + 2 * KD + k] = (k == t) ? 1.f : 0.f;
+                }
+            }
+            v[1] = w;
+        }
+    }
+    block_sum<NV>(v, red, partials + (size_t)blockIdx.x * NV);
+}
+
+// out = [loss, sum w (the pixel count without weights), bad targets, CE, Dice, a[N][KD], b[N][KD]]:
+//   dDice / dp_ik = a_nk [t_i = k] + b_nk  on the valid pixels of image n (what the backward kernel needs from the sums)
+// One workgroup; wave w sums the partial rows of images w, w + 4, .. in double (lanes stride the rows, then the cross-lane
+// tree), thread 0 adds the four waves' totals in wave order.
+template <int KD>
+__global__ __launch_bounds__(MEDT_THREADS) void seg_loss_finalize_kernel(const float* __restrict__ partials,
+                                                                         float* __restrict__ out, int N, int bpi,
+                                                                         float ce_scale, float dice_scale, float eps) {
+    constexpr int NV = 3 + 3 * KD;
+    MEDT_STATIC_SHARED double tot[MEDT_WAVES * 4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double s_nll = 0.0, s_w = 0.0, s_bad = 0.0, s_dice = 0.0;
+    for (int n = wave; n < N; n += MEDT_WAVES) {
+        double acc[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+        for (int b = lane; b < bpi; b += 64) {
+            const float* pp = partials + ((size_t)n * bpi + b) * NV;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) acc[j] += (double)pp[j];
+        }
+#pragma unroll
+        for (int j = 0; j < NV; ++j) acc[j] = wave_sum_d(acc[j]);
+        s_nll += acc[0];
+        s_w += acc[1];
+        s_bad += acc[2];
+        if constexpr (KD > 0) {
+            const double nk = (double)N * KD;
+#pragma unroll
+            for (int k = 0; k < KD; ++k) {
+                const double num = 2.0 * acc[3 + k] + (double)eps;
+                const double D = acc[3 + KD + k] + acc[3 + 2 * KD + k] + (double)eps;
+                s_dice += num / D;
+                if (lane == 0) {
+                    out[5 + (size_t)n * KD + k] = (float)(-2.0 / (D * nk));
+                    out[5 + ((size_t)N + n) * KD + k] = (float)(num / (D * D * nk));
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        tot[wave * 4] = s_nll;
+        tot[wave * 4 + 1] = s_w;
+        tot[wave * 4 + 2] = s_bad;
+        tot[wave * 4 + 3] = s_dice;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int w = 0; w < MEDT_WAVES; ++w)
+            for (int j = 0; j < 4; ++j) t[j] += tot[w * 4 + j];
+        const double ce = t[0] / t[1];                              // no counted weight: 0/0 = NaN, as in torch
+        double dice = 0.0;
+        if constexpr (KD > 0) dice = 1.0 - t[3] / ((double)N * KD);
+        double loss = 0.0;                                          // a switched-off term stays out (0 * NaN)
+        if (ce_scale != 0.f) loss += (double)ce_scale * ce;
+        if (dice_scale != 0.f) loss += (double)dice_scale * dice;
+        out[0] = (float)loss;
+        out[1] = (float)t[1];
+        out[2] = (float)t[2];
+        out[3] = (float)ce;
+        out[4] = (float)dice;
+    }
+}
+
+// dlogits[n,j,p] = dloss * ( ce_scale * w[t] / sum w * (p_j - [j == t])  +  dice_scale * p_j * (g_j - sum_k p_k g_k) ),
+// g_k = a_nk [t == k] + b_nk;  pixels that are not valid get 0 in every class
+template <int KD>
+__global__ __launch_bounds__(MEDT_THREADS) void seg_loss_bwd_kernel(const float* __restrict__ logits,
+                                                                    const int64_t* __restrict__ target,
+                                                                    const float* __restrict__ weight,
+                                                                    const float* __restrict__ out,
+                                                                    const float* __restrict__ dloss,
+                                                                    float* __restrict__ dlogits, int N, int K, int HW,
+                                                                    int bpi, int ignore, float ce_scale, float dice_scale) {
+    const int n = blockIdx.x / bpi;
+    const int p = (blockIdx.x - n * bpi) * MEDT_THREADS + threadIdx.x;
+    if (p >= HW) return;
+    const int64_t t = target[(size_t)n * HW + p];
+    const float* lp = logits + (size_t)n * K * HW + p;
+    float* dp = dlogits + (size_t)n * K * HW + p;
+    if (t == ignore || t < 0 || t >= K) {
+        for (int k = 0; k < K; ++k) dp[(size_t)k * HW] = 0.f;
+        return;
+    }
+    const float dl = dloss ? dloss[0] : 1.f;
+    const float cs = ce_scale != 0.f ? ce_scale * (weight ? weight[t] : 1.f) / out[1] * dl : 0.f;
+    if constexpr (KD == 0) {
+        float m = lp[0];
+        for (int k = 1; k < K; ++k) m = fmaxf(m, lp[(size_t)k * HW]);
+        float sum = 0.f;
+        for (int k = 0; k < K; ++k) sum += __expf(lp[(size_t)k * HW] - m);
+        const float inv = 1.f / sum;
+        for (int k = 0; k < K; ++k) {
+            const float pk = __expf(lp[(size_t)k * HW] - m) * inv;
+            dp[(size_t)k * HW] = (pk - (k == t ? 1.f : 0.f)) * cs;
+        }
+    } else {
+        const float* ca = out + 5 + (size_t)n * KD;              // workgroup-uniform: one image per workgroup
+        const float* cb = out + 5 + ((size_t)N + n) * KD;
+        const float ds = dice_scale * dl;
+        float l[KD], g[KD];
+#pragma unroll
+        for (int k = 0; k < KD; ++k) l[k] = lp[(size_t)k * HW];
+        float m = l[0];
+#pragma unroll
+        for (int k = 1; k < KD; ++k) m = fmaxf(m, l[k]);
+        float sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < KD; ++k) { l[k] = __expf(l[k] - m); sum += l[k]; }
+        const float inv = 1.f / sum;
+        float dot = 0.f;
+#pragma unroll
+        for (int k = 0; k < KD; ++k) {
+            l[k] *= inv;
+            g[k] = ds * ((k == t ? ca[k] : 0.f) + cb[k]);
+            dot += l[k] * g[k];
+        }
+#pragma unroll
+        for (int k = 0; k < KD; ++k) dp[(size_t)k * HW] = l[k] * (g[k] - dot) + cs * (l[k] - (k == t ? 1.f : 0.f));
+    }
+}
+
+int seg_loss_bpi(int HW) { return cdiv(HW, MEDT_THREADS); }
+size_t seg_loss_partials(int N, int K, int HW) { return (size_t)N * seg_loss_bpi(HW) * (3 + (K <= 8 ? 3 * K : 0)); }
+size_t seg_loss_out_floats(int N, int K) { return 5 + 2 * (size_t)N * K; }
+
+// SEG_LOSS_KD(X): X(KD) for the instance that serves (K, Dice on or off)
+#define SEG_LOSS_KD(X)                                                                                                 \
+    switch (dice_scale != 0.f ? K : 0) {                                                                               \
+        case 0: X(0); break;                                                                                           \
+        case 2: X(2); break;                                                                                           \
+        case 3: X(3); break;                                                                                           \
+        case 4: X(4); break;                                                                                           \
+        case 5: X(5); break;                                                                                           \
+        case 6: X(6); break;                                                                                           \
+        case 7: X(7); break;                                                                                           \
+        case 8: X(8); break;                                                                                           \
+        default: set_error("seg_loss: soft Dice needs 2 <= K <= 8 classes (K = %d)", K); return MEDT_EINVAL;           \
+    }
+
+int seg_loss_fwd(const float* logits, const int64_t* target, const float* weight, float* partials, float* out, int N, int K,
+                 int HW, int ignore, float ce_scale, float dice_scale, float eps, hipStream_t s) {
+    const int bpi = seg_loss_bpi(HW);
+#define SEG_LOSS_FWD(KD)                                                                                               \
+    hipLaunchKernelGGL(seg_loss_fwd_kernel<KD>, dim3((unsigned)N * bpi), dim3(MEDT_THREADS), 0, s, logits, target, weight, \
+                       partials, K, HW, bpi, ignore)
+    SEG_LOSS_KD(SEG_LOSS_FWD)
+#undef SEG_LOSS_FWD
+    int rc = launch_status("seg_loss_fwd");
+    if (rc) return rc;
+#define SEG_LOSS_FIN(KD)                                                                                               \
+    hipLaunchKernelGGL(seg_loss_finalize_kernel<KD>, dim3(1), dim3(MEDT_THREADS), 0, s, partials, out, N, bpi, ce_scale, \
+                       dice_scale, eps)
+    SEG_LOSS_KD(SEG_LOSS_FIN)
+#undef SEG_LOSS_FIN
+    return launch_status("seg_loss_finalize");
+}
+
+int seg_loss_bwd(const float* logits, const int64_t* target, const float* weight, const float* out, const float* dloss,
+                 float* dlogits, int N, int K, int HW, int ignore, float ce_scale, float dice_scale, hipStream_t s) {
+    const int bpi = seg_loss_bpi(HW);
+#define SEG_LOSS_BWD(KD)                                                                                               \
+    hipLaunchKernelGGL(seg_loss_bwd_kernel<KD>, dim3((unsigned)N * bpi), dim3(MEDT_THREADS), 0, s, logits, target, weight, \
+                       out, dloss, dlogits, N, K, HW, bpi, ignore, ce_scale, dice_scale)
+    SEG_LOSS_KD(SEG_LOSS_BWD)
+#undef SEG_LOSS_BWD
+    return launch_status("seg_loss_bwd");
+}
+#undef SEG_LOSS_KD
+
+// --------------------------------------------------------------------------- //
 // AxialAttention_gated_sig (reference lib/models/model_codes.py:279-280, 292-293): the four gates enter through a sigmoid
 // --------------------------------------------------------------------------- //
 __global__ void gate_sigmoid_fwd_kernel(const float* f_qr, const float* f_kr, const float* f_sve, const float* f_sv,

@@ -890,6 +890,42 @@ int medt_ce_bwd(const float* logits, const int64_t* target, const float* loss_ou
     if (!logits || !target || !loss_out || !dlogits) { set_error("ce bwd: bad arguments"); return MEDT_EINVAL; }
     return ce_bwd(logits, target, loss_out, dloss, dlogits, N, K, HW, ignore_index, (hipStream_t)stream);
 }
+// sizes, scales and the class limits of medt_seg_loss_*: Dice keeps its per-class sums in registers (2 <= K <= 8)
+static int seg_loss_args(const char* what, int N, int K, int HW, float dice_scale, float eps) {
+    if (N < 1 || K < 1 || HW < 1 || !(eps >= 0.f)) {
+        set_error("%s: bad arguments (N %d, K %d, HW %d, eps %g)", what, N, K, HW, (double)eps); return MEDT_EINVAL;
+    }
+    if (dice_scale != 0.f && (K < 2 || K > 8)) {
+        set_error("%s: soft Dice needs 2 <= K <= 8 classes (K = %d)", what, K); return MEDT_EINVAL;
+    }
+    if ((double)N * seg_loss_bpi(HW) >= 2147483648.0 || (double)N * K >= 2147483648.0) {
+        set_error("%s: %d images of %d pixels, %d classes: too large a grid", what, N, HW, K); return MEDT_EUNSUPPORTED;
+    }
+    return MEDT_OK;
+}
+size_t medt_seg_loss_workspace(int N, int K, int HW) {
+    if (seg_loss_args("seg_loss workspace", N, K, HW, 0.f, 0.f)) return 0;
+    return seg_loss_partials(N, K, HW);
+}
+size_t medt_seg_loss_out_floats(int N, int K) {
+    if (seg_loss_args("seg_loss out_floats", N, K, 1, 0.f, 0.f)) return 0;
+    return seg_loss_out_floats(N, K);
+}
+int medt_seg_loss_fwd(const float* logits, const int64_t* target, const float* class_weight, float* partials, float* out,
+                      int N, int K, int HW, int ignore_index, float ce_scale, float dice_scale, float eps, void* stream) {
+    if (!logits || !target || !partials || !out) { set_error("seg_loss fwd: null pointer"); return MEDT_EINVAL; }
+    if (int rc = seg_loss_args("seg_loss fwd", N, K, HW, dice_scale, eps)) return rc;
+    return seg_loss_fwd(logits, target, class_weight, partials, out, N, K, HW, ignore_index, ce_scale, dice_scale, eps,
+                        (hipStream_t)stream);
+}
+int medt_seg_loss_bwd(const float* logits, const int64_t* target, const float* class_weight, const float* out,
+                      const float* dloss, float* dlogits, int N, int K, int HW, int ignore_index, float ce_scale,
+                      float dice_scale, float eps, void* stream) {
+    if (!logits || !target || !out || !dlogits) { set_error("seg_loss bwd: null pointer"); return MEDT_EINVAL; }
+    if (int rc = seg_loss_args("seg_loss bwd", N, K, HW, dice_scale, eps)) return rc;
+    return seg_loss_bwd(logits, target, class_weight, out, dloss, dlogits, N, K, HW, ignore_index, ce_scale, dice_scale,
+                        (hipStream_t)stream);
+}
 int medt_adam_step(float* p, const float* g, float* m, float* v, float* state, size_t n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, float gscale, void* stream) {
     if (!p || !g || !m || !v || !state) { set_error("adam: null pointer"); return MEDT_EINVAL; }

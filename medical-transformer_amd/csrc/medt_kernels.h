@@ -129,6 +129,14 @@ int ce_fwd(const float* logits, const int64_t* target, float* partials, float* l
            hipStream_t s);
 int ce_bwd(const float* logits, const int64_t* target, const float* loss_out, const float* dloss, float* dlogits, int N,
            int K, int HW, int ignore, hipStream_t s);
+// class-weighted cross entropy + per-image soft Dice (weight may be null; Dice needs 2 <= K <= 8): medt_abi.h
+int seg_loss_bpi(int HW);
+size_t seg_loss_partials(int N, int K, int HW);
+size_t seg_loss_out_floats(int N, int K);
+int seg_loss_fwd(const float* logits, const int64_t* target, const float* weight, float* partials, float* out, int N, int K,
+                 int HW, int ignore, float ce_scale, float dice_scale, float eps, hipStream_t s);
+int seg_loss_bwd(const float* logits, const int64_t* target, const float* weight, const float* out, const float* dloss,
+                 float* dlogits, int N, int K, int HW, int ignore, float ce_scale, float dice_scale, hipStream_t s);
 // gated_sig: eff[k] = sigmoid(*f[k]) (k: f_qr, f_kr, f_sve, f_sv);  dgate[k] = d_eff[k] * eff[k] * (1 - eff[k])
 int gate_sigmoid_fwd(const float* f_qr, const float* f_kr, const float* f_sve, const float* f_sv, float* eff, hipStream_t s);
 int gate_sigmoid_bwd(const float* d_eff, const float* eff, float* dgate, hipStream_t s);

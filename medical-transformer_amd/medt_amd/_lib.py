@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede CDLL: provides the HIP runtime the lib
 from .build import LIB_PATH
 
 _lib = None
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class MedtError(RuntimeError):
@@ -141,6 +141,10 @@ SIGNATURES = {
                               C.c_void_p]),
     "medt_ce_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_void_p]),
+    "medt_seg_loss_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "medt_seg_loss_out_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "medt_seg_loss_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p]),
+    "medt_seg_loss_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p]),
     "medt_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float,
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "medt_relu_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

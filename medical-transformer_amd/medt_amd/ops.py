@@ -404,6 +404,88 @@ def raise_on_bad_targets(out, K):
 
 
 # --------------------------------------------------------------------------- #
+# class-weighted cross entropy + soft Dice
+# --------------------------------------------------------------------------- #
+class SegLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, weight, ce, dice, eps, ignore_index):
+        _require_device(logits)
+        lib = L.lib()
+        logits, target = logits.contiguous(), target.contiguous()
+        N, K = logits.shape[0], logits.shape[1]
+        HW = logits[0, 0].numel()
+        nws, nout = lib.medt_seg_loss_workspace(N, K, HW), lib.medt_seg_loss_out_floats(N, K)
+        if not nws or not nout:
+            raise L.MedtError(f"seg_loss: {lib.medt_last_error().decode()}")
+        partials = torch.empty((nws,), device=logits.device, dtype=torch.float32)
+        out = torch.empty((nout,), device=logits.device, dtype=torch.float32)
+        L.check(lib.medt_seg_loss_fwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), partials.data_ptr(), out.data_ptr(),
+                                      N, K, HW, ignore_index, ce, dice, eps, _stream()), "medt_seg_loss_fwd")
+        ctx.save_for_backward(logits, target, out, weight)
+        ctx.cfg = (ce, dice, eps, ignore_index)
+        loss = out[0]
+        ctx.mark_non_differentiable(out)
+        ctx.set_materialize_grads(False)          # no zero-fill launch for the gradient of the non-differentiable output
+        return loss, out
+
+    @staticmethod
+    def backward(ctx, dloss, _dout):
+        if dloss is None:
+            return (None,) * 7
+        lib = L.lib()
+        logits, target, out, weight = ctx.saved_tensors
+        ce, dice, eps, ignore_index = ctx.cfg
+        N, K = logits.shape[0], logits.shape[1]
+        HW = logits[0, 0].numel()
+        dloss = dloss.contiguous().float()
+        dlogits = torch.empty_like(logits)
+        L.check(lib.medt_seg_loss_bwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), out.data_ptr(), dloss.data_ptr(),
+                                      dlogits.data_ptr(), N, K, HW, ignore_index, ce, dice, eps, _stream()),
+                "medt_seg_loss_bwd")
+        return (dlogits,) + (None,) * 6
+
+
+def seg_loss(logits, target, weight=None, ce=1.0, dice=0.0, eps=1.0, ignore_index=-100):
+    """ce * CE + dice * Dice of (N,K,H,W) float32 logits against (N,H,W) int64 class indices, p = softmax over the classes.
+
+    CE is F.cross_entropy(logits, target, weight=weight, ignore_index=ignore_index) with mean reduction -- what the
+    reference's LogNLLLoss(weight=...) computes (metrics.py:17-20): sum w[t] nll / sum w[t] over the valid pixels (target
+    not `ignore_index`), NaN when nothing is counted.  `weight`: a float32 tensor of K class weights on the logits'
+    device, or None (all 1).
+
+    Dice is 1 - mean over images n and classes k of (2 I_nk + eps) / (P_nk + T_nk + eps) with I_nk = sum p_ik [t_i = k],
+    P_nk = sum p_ik, T_nk = sum [t_i = k] over the valid pixels of image n ONLY (2 <= K <= 8).  `eps` (default 1) keeps an
+    image whose pixels are all ignored, or a class that is neither present nor predicted, finite with a zero or finite
+    gradient.  Per image, not per batch, on purpose: under data parallel with equal shards the mean of the ranks'
+    gradients is then exactly the gradient of the global batch, without another collective.  The weighted CE under data
+    parallel is a mean of per-rank weighted means, as with DistributedDataParallel around F.cross_entropy(weight=...).
+
+    Either scale may be 0; that term is then left out (the weighted CE alone takes any K).  Two forward launches and one backward launch whatever the options, no float atomics: eager and replayed
+    steps agree bit for bit.  Class indices outside [0, K) that are not `ignore_index` are handled as in cross_entropy()
+    above: excluded, counted, raised on here (outside graph capture) and by TrainStep.check_targets()."""
+    if logits.dim() < 2 or logits.dtype != torch.float32:
+        raise L.MedtError("seg_loss: float32 (N,K,...) logits expected")
+    if target.dtype != torch.int64 or target.device != logits.device or target.numel() * logits.shape[1] != logits.numel():
+        raise L.MedtError("seg_loss: int64 (N,...) class-index targets on the logits' device expected")
+    K = logits.shape[1]
+    if weight is not None:
+        if (not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.dim() != 1 or weight.numel() != K
+                or weight.device != logits.device):
+            raise L.MedtError(f"seg_loss: weight must be a float32 tensor of {K} class weights on the logits' device")
+        weight = weight.detach().contiguous()
+    ce, dice, eps = float(ce), float(dice), float(eps)
+    if dice != 0.0 and not 2 <= K <= 8:
+        raise L.MedtError(f"seg_loss: soft Dice needs 2 <= K <= 8 classes (K = {K})")
+    if not eps >= 0.0:
+        raise L.MedtError("seg_loss: eps >= 0 expected")
+    loss, out = SegLossFn.apply(logits, target, weight, ce, dice, eps, int(ignore_index))
+    loss._medt_ce_out = out                       # [loss, sum of counted weights, out-of-range targets, CE, Dice, ...]
+    if CHECK_TARGETS and not torch.cuda.is_current_stream_capturing():
+        raise_on_bad_targets(out, K)
+    return loss
+
+
+# --------------------------------------------------------------------------- #
 # segmentation scoring (replaces performancemetrics_*.m)
 # --------------------------------------------------------------------------- #
 def seg_counts(logits, target, threshold=0.5):

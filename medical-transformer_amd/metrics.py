@@ -1,6 +1,8 @@
 """Drop-in for the reference's metrics.py.  LogNLLLoss.forward is plain mean cross entropy
 (reference metrics.py:17-20; the log() line is commented out there) and runs as the HIP kernel pair
-medt_ce_fwd / medt_ce_bwd.  The classwise helpers are imported by train.py:23 but never called."""
+medt_ce_fwd / medt_ce_bwd; with class weights (F.cross_entropy(weight=...) in the reference) as medt_seg_loss_fwd / _bwd, which
+also carry the soft Dice term of DiceCELoss (not in the reference).  The classwise helpers are imported by train.py:23 but
+never called."""
 import torch
 from torch.nn.modules.loss import _WeightedLoss
 
@@ -18,8 +20,27 @@ class LogNLLLoss(_WeightedLoss):
 
     def forward(self, y_input, y_target):
         if self.weight is not None:
-            raise NotImplementedError("class weights are never used by train.py (criterion = LogNLLLoss())")
+            return medt_amd.seg_loss(y_input, y_target, weight=self.weight, ignore_index=self.ignore_index)
         return medt_amd.cross_entropy(y_input, y_target, self.ignore_index)
+
+
+class DiceCELoss(torch.nn.Module):
+    """ce * (class-weighted) cross entropy + dice * soft Dice, one kernel pair (medt_amd.seg_loss has the formulas).
+
+    The Dice term is per image and per class over the non-ignored pixels, 2 <= K <= 8 classes; `eps` keeps empty images and
+    absent classes finite.  Under data parallel the Dice gradient of equal shards averages to the global batch's; the
+    weighted cross entropy is a mean of per-rank weighted means, as with DistributedDataParallel."""
+
+    def __init__(self, weight=None, ce=1.0, dice=1.0, eps=1.0, ignore_index=-100):
+        super().__init__()
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32).reshape(-1)
+        self.register_buffer("weight", weight)
+        self.ce, self.dice, self.eps, self.ignore_index = float(ce), float(dice), float(eps), ignore_index
+
+    def forward(self, y_input, y_target):
+        return medt_amd.seg_loss(y_input, y_target, weight=self.weight, ce=self.ce, dice=self.dice, eps=self.eps,
+                                 ignore_index=self.ignore_index)
 
 
 def classwise_iou(output, gt):

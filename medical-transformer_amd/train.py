@@ -11,6 +11,8 @@ Differences, all host-side plumbing:
   * batches are decoded, pinned and copied to the GPU one step ahead (medt_amd.data.DevicePrefetcher);
   * the step runs as a replayed hipGraph with a fused flat Adam (medt_amd.trainer); --eager disables it;
   * --synthetic N writes N synthetic PNG pairs into --train_dataset first (BASELINE.json config 1 plumbing);
+  * --loss {ce,dice,ce+dice} and --class_weights "w0,w1" pick the criterion (metrics.DiceCELoss / LogNLLLoss(weight)); the
+    defaults are the reference's LogNLLLoss();
   * the per-step threshold-and-copy-to-host of the output (train.py:142-152) is dropped: its result is unused.
 """
 import argparse
@@ -22,7 +24,7 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 
 import lib
-from metrics import LogNLLLoss
+from metrics import DiceCELoss, LogNLLLoss
 from medt_amd import dp
 from medt_amd.data import DevicePrefetcher, imwrite, make_synthetic_dataset
 from medt_amd.optim import FlatAdam
@@ -51,10 +53,32 @@ parser.add_argument('--device', default='cuda', type=str)
 parser.add_argument('--gray', default='no', type=str)
 parser.add_argument('--synthetic', type=int, default=0, help='write this many synthetic PNG pairs into the dataset dirs first')
 parser.add_argument('--eager', action='store_true', help='no hipGraph replay')
+parser.add_argument('--loss', default='ce', choices=['ce', 'dice', 'ce+dice'], help='cross entropy, soft Dice or their sum (default: ce)')
+parser.add_argument('--class_weights', default=None, type=str, help='comma-separated class weights of the cross entropy, e.g. "1,3"')
+
+NUM_CLASSES = 2          # every network of lib.models ends in a 2-channel adjust convolution
+
+
+def make_criterion(loss, class_weights):
+    weight = None
+    if class_weights is not None:
+        try:
+            weight = [float(w) for w in class_weights.split(",")]
+        except ValueError:
+            raise SystemExit("--class_weights: comma-separated numbers expected, got %r" % class_weights)
+        if len(weight) != NUM_CLASSES:
+            raise SystemExit("--class_weights: %d weights given, the networks have %d classes" % (len(weight), NUM_CLASSES))
+        if loss == "dice":
+            raise SystemExit("--class_weights weigh the cross entropy: use --loss ce or ce+dice")
+        weight = torch.tensor(weight, dtype=torch.float32)
+    if loss == "ce":
+        return LogNLLLoss() if weight is None else LogNLLLoss(weight=weight)         # the defaults: reference train.py:110
+    return DiceCELoss(weight=weight, ce=0.0 if loss == "dice" else 1.0, dice=1.0)
 
 
 def main():
     args = parser.parse_args()
+    criterion = make_criterion(args.loss, args.class_weights)      # (a bad --class_weights ends the run before any work)
     direc, modelname, imgsize = args.direc, args.modelname, args.imgsize
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -104,7 +128,7 @@ def main():
     model.to(device)
     dp.broadcast_parameters(model)
 
-    criterion = LogNLLLoss()
+    criterion.to(device)
     optimizer = FlatAdam(list(model.parameters()), lr=args.learning_rate, weight_decay=1e-5)
     train_step = TrainStep(model, optimizer, criterion, use_graph=not args.eager)
     infer_step = InferStep(model, use_graph=not args.eager)
