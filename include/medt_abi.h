@@ -34,6 +34,8 @@
 extern "C" {
 #endif
 
+/* 11: medt_seg_loss_*.  The medt_augment_* entry points were added under the same number: additions only, nothing that
+ * version 11 declared was removed or changed, so a caller built against the earlier header keeps working. */
 #define MEDT_ABI_VERSION 11
 
 #define MEDT_OK            0
@@ -390,6 +392,37 @@ int medt_window_gather(const float* image, float* windows, const int32_t* oy, co
                        int ny, int nx, void* stream);
 int medt_window_blend(const float* win_logits, float* blended, uint8_t* mask, const int32_t* oy, const int32_t* ox, int K,
                       int H, int W, int S, int ny, int nx, float threshold, void* stream);
+
+/* Joint augmentation of a training batch on the device (medt_amd/augment.py; the reference's JointTransform2D.__call__,
+ * utils.py:70-98, does it per item with torchvision on the host): random crop, horizontal flip, colour jitter (image only)
+ * and a random affine map (image and mask), in that order.
+ * image (N,H,W,C) uint8, C = 1 or 3, channels as decoded; mask (N,H,W) uint8 -> out_image (N,C,th,tw) float32 in [0,1],
+ * out_mask (N,th,tw) int64.  params: a DEVICE table of N records of medt_augment_param_floats() floats, drawn on the host:
+ *   [0] cy [1] cx  crop origin    [2] flip (!= 0)    [3] identity (!= 0: the affine step is skipped, no float round trip)
+ *   [4..9] m00 m01 m02 m10 m11 m12   the INVERSE affine map, output pixel centre -> cropped image
+ *   [10..13] operation of jitter slot k: 0 none, 1 brightness, 2 contrast, 3 saturation, 4 hue    [14..17] its factor
+ *   [18..19] reserved, 0
+ * Output pixel (i, j): fx = m00 (j+.5) + m01 (i+.5) + m02, fy = m10 (j+.5) + m11 (i+.5) + m12, sx = floor(fx), sy = floor(fy)
+ * (PIL's Image.transform(AFFINE, NEAREST)).  Outside [0,tw) x [0,th) -- tested on the floats, so non-finite or huge
+ * coordinates are outside -- the image receives 0.0 and the mask 0, neither jittered.  Flip: sx -> tw-1-sx.  Source pixel
+ * (cy+sy, cx+sx), clamped to the input: no table makes a kernel read out of bounds.  v = u8 / 255 (IEEE division), then the
+ * slots in order, torchvision's float path, g = 0.299 c0 + 0.587 c1 + 0.114 c2 over the channels as stored:
+ *   brightness clamp(b v, 0, 1); saturation clamp(s v + (1-s) g, 0, 1); contrast clamp(c v + (1-c) mean_g, 0, 1);
+ *   hue: RGB -> HSV, H = (H + h) mod 1, HSV -> RGB (hexcone).  C == 1: g = v, saturation and hue are the identity.
+ * mean_g: the mean of g over the cropped th x tw image after the slots in front of the record's (one) contrast slot.
+ *
+ * medt_augment_stats computes the per-image sums of g into workspace (medt_augment_workspace() floats: partial sums, then
+ * N means); fixed summation order, no atomics, the same bits on every run.  medt_augment_apply does everything else: one
+ * launch; use_stats != 0 reads the sums (call stats first), use_stats == 0 takes mean_g = 0 -- for batches without a
+ * contrast slot, whose workspace may be NULL.  A non-NULL workspace receives the N means used.  16-byte stores when
+ * tw % 4 == 0 and both outputs are 16-byte aligned, element stores otherwise.  N*H*W*C and N*C*th*tw must stay below 2^31
+ * (MEDT_EUNSUPPORTED above). */
+size_t medt_augment_param_floats(void);
+size_t medt_augment_workspace(int N, int th, int tw);
+int medt_augment_stats(const uint8_t* image, const float* params, float* workspace, int N, int H, int W, int C, int th,
+                       int tw, void* stream);
+int medt_augment_apply(const uint8_t* image, const uint8_t* mask, const float* params, float* workspace, float* out_image,
+                       int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, void* stream);
 
 #ifdef __cplusplus
 }

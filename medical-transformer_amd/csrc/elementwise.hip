@@ -5,6 +5,7 @@
 //   cross-entropy loss                                       (metrics.py:17-20)
 //   Adam with coupled L2 weight decay over a flat buffer     (train.py:111-112,161)
 //   sliding-window gather / blend for images larger than the network input (not in the reference)
+//   joint augmentation of uint8 batches: crop, flip, colour jitter, affine (utils.py:70-98)
 // All HBM-bound: one element per lane, NCHW rows coalesced, per-channel constants via scalar loads.
 #include "medt_kernels.h"
 #include <stdint.h>
@@ -1147,6 +1148,251 @@ int window_blend(const float* win, float* blended, uint8_t* mask, const int32_t*
         hipLaunchKernelGGL((window_blend_kernel<false>), dim3(grid_strided(items)), dim3(MEDT_THREADS), 0, s, win, blended,
                            mask, oy, ox, k0, K, H, W, S, ny, nx, threshold, items);
     return launch_status("window_blend");
+}
+
+// --------------------------------------------------------------------------- //
+// Joint augmentation of a training batch on the device (medt_amd/augment.py; reference utils.py:70-98 does it per item
+// with torchvision on the host): uint8 HWC images (N,H,W,C) + uint8 masks (N,H,W) -> float32 (N,C,th,tw) in [0,1] and
+// int64 (N,th,tw).  One record of AUG_P floats per image, drawn on the host and kept in a DEVICE table, so one launch
+// geometry serves every draw:
+//   [0] cy  [1] cx  crop origin          [2] flip != 0          [3] identity != 0: no affine step
+//   [4..9]  m00 m01 m02 m10 m11 m12      inverse affine map, output pixel centre -> cropped image
+//   [10..13] operation of jitter slot k  0 none, 1 brightness, 2 contrast, 3 saturation, 4 hue
+//   [14..17] factor of jitter slot k     [18..19] reserved, 0
+// Output pixel (i, j):  (fx, fy) = m (j + .5, i + .5);  outside [0,tw) x [0,th) -- tested on the FLOATS, so NaN / huge
+// coordinates are outside -- the image gets 0 and the mask class 0;  sx = floor(fx) (mirrored when flipped), sy = floor(fy);
+// source pixel (cy + sy, cx + sx), clamped to the input like window_gather (no table makes a read leave the input);
+// v = u8 / 255 (IEEE division: to_tensor's bits), then the jitter slots in order -- torchvision's float path.
+// The source offset (cy*W + cx)*C is arbitrary, so the C bytes of a pixel are fetched as bytes: a 4-pixel identity run of
+// 12 bytes is dword aligned for one origin in four, and neighbouring lanes' bytes share cache lines either way.
+// --------------------------------------------------------------------------- //
+constexpr int AUG_P = 20;
+constexpr int AUG_CY = 0, AUG_CX = 1, AUG_FLIP = 2, AUG_IDENT = 3, AUG_M = 4, AUG_OP = 10, AUG_FAC = 14;
+constexpr float AUG_BRIGHTNESS = 1.f, AUG_CONTRAST = 2.f, AUG_SATURATION = 3.f, AUG_HUE = 4.f;
+
+size_t augment_param_floats() { return AUG_P; }
+int augment_parts(int th, int tw) { return (int)min(((size_t)th * tw + 1023) / 1024, (size_t)32); }
+
+__device__ __forceinline__ float aug_clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
+
+template <int C>
+__device__ __forceinline__ float aug_gray(const float (&v)[C]) {
+    if (C == 3) return 0.299f * v[0] + 0.587f * v[1 % C] + 0.114f * v[2 % C];      // channels AS STORED (BGR handed over as RGB)
+    return v[0];
+}
+
+// torchvision.transforms.functional_tensor: _rgb2hsv, h = (h + hf) mod 1, _hsv2rgb (hexcone)
+__device__ __forceinline__ void aug_hue(float (&v)[3], float hf) {
+    const float r = v[0], g = v[1], b = v[2];
+    const float maxc = fmaxf(r, fmaxf(g, b)), minc = fminf(r, fminf(g, b));
+    const bool eqc = maxc == minc;
+    const float cr = maxc - minc;
+    const float s = cr / (eqc ? 1.f : maxc);
+    const float crd = eqc ? 1.f : cr;
+    const float rc = (maxc - r) / crd, gc = (maxc - g) / crd, bc = (maxc - b) / crd;
+    float h = maxc == r ? bc - gc : (maxc == g ? 2.f + rc - bc : 4.f + gc - rc);
+    h = fmodf(h / 6.f + 1.f, 1.f);
+    h += hf;
+    h -= floorf(h);
+    const float h6 = h * 6.f, fi = floorf(h6), f = h6 - fi;
+    const int i = (fi >= 0.f && fi < 7.f) ? (int)fi % 6 : 0;
+    const float p = aug_clamp01(maxc * (1.f - s)), q = aug_clamp01(maxc * (1.f - s * f)),
+                t = aug_clamp01(maxc * (1.f - s * (1.f - f)));
+    switch (i) {
+        case 0: v[0] = maxc; v[1] = t; v[2] = p; break;
+        case 1: v[0] = q; v[1] = maxc; v[2] = p; break;
+        case 2: v[0] = p; v[1] = maxc; v[2] = t; break;
+        case 3: v[0] = p; v[1] = q; v[2] = maxc; break;
+        case 4: v[0] = t; v[1] = p; v[2] = maxc; break;
+        default: v[0] = maxc; v[1] = p; v[2] = q; break;
+    }
+}
+__device__ __forceinline__ void aug_hue(float (&)[1], float) {}
+
+// the jitter slots of one record on one pixel.  UNTIL_CONTRAST: stop in front of the first contrast slot and say whether
+// there is one (augment_stats: mean_g is the mean grey of the image at that point)
+template <int C, bool UNTIL_CONTRAST>
+__device__ __forceinline__ bool aug_jitter(float (&v)[C], const float* __restrict__ rec, float mean_g) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float op = rec[AUG_OP + k], fac = rec[AUG_FAC + k];
+        if (op == AUG_BRIGHTNESS) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[c] = aug_clamp01(fac * v[c]);
+        } else if (op == AUG_CONTRAST) {
+            if (UNTIL_CONTRAST) return true;
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[c] = aug_clamp01(fac * v[c] + (1.f - fac) * mean_g);
+        } else if (op == AUG_SATURATION) {
+            if (C == 3) {
+                const float g = aug_gray<C>(v);
+#pragma unroll
+                for (int c = 0; c < C; ++c) v[c] = aug_clamp01(fac * v[c] + (1.f - fac) * g);
+            }
+        } else if (op == AUG_HUE) {
+            aug_hue(v, fac);
+        }
+    }
+    return false;
+}
+
+struct AugCrop {
+    int cy, cx;
+};
+// the origin as integers inside the input, whatever the table holds (fmaxf(NaN, 0) = 0)
+__device__ __forceinline__ AugCrop aug_origin(const float* __restrict__ rec, int H, int W) {
+    AugCrop o;
+    o.cy = (int)fminf(fmaxf(rec[AUG_CY], 0.f), (float)(H - 1));
+    o.cx = (int)fminf(fmaxf(rec[AUG_CX], 0.f), (float)(W - 1));
+    return o;
+}
+
+// partials[n][part] = sum of the grey value, in front of the record's contrast slot, over the part's share of the CROPPED
+// th x tw image (0 when the record has no contrast).  Fixed order: a thread's pixels ascending, the xor tree of the wave,
+// the four waves ascending; augment_apply adds the parts ascending.  No atomics.
+template <int C>
+__global__ __launch_bounds__(MEDT_THREADS) void augment_stats_kernel(const uint8_t* __restrict__ image,
+                                                                     const float* __restrict__ params,
+                                                                     float* __restrict__ partials, int H, int W, int th,
+                                                                     int tw, int parts) {
+    MEDT_STATIC_SHARED float red[MEDT_WAVES];
+    const int n = blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
+    const float* rec = params + (size_t)n * AUG_P;
+    const AugCrop o = aug_origin(rec, H, W);
+    const int total = th * tw, chunk = (total + parts - 1) / parts;
+    const int p1 = min(total, (part + 1) * chunk);
+    float sum = 0.f;
+    for (int p = part * chunk + tid; p < p1; p += MEDT_THREADS) {
+        const int i = p / tw, j = p - i * tw;
+        const int y = min(o.cy + i, H - 1), x = min(o.cx + j, W - 1);
+        const uint8_t* src = image + (((size_t)n * H + y) * W + x) * C;
+        float v[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = (float)src[c] / 255.f;
+        if (aug_jitter<C, true>(v, rec, 0.f)) sum += aug_gray<C>(v);
+    }
+    sum = wave_sum(sum);
+    if ((tid & 63) == 0) red[tid >> 6] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < MEDT_WAVES; ++w) s += red[w];
+        partials[(size_t)n * parts + part] = s;
+    }
+}
+
+struct alignas(16) AugLabel2 {
+    int64_t a, b;
+};
+
+// a work-item: 4 consecutive output x of one row of image blockIdx.y, all channels.  means (N floats behind the partials)
+// receives the mean grey the contrast slot used, 0 without statistics.
+template <int C, bool VEC4>
+__global__ __launch_bounds__(MEDT_THREADS) void augment_apply_kernel(const uint8_t* __restrict__ image,
+                                                                     const uint8_t* __restrict__ mask,
+                                                                     const float* __restrict__ params,
+                                                                     const float* __restrict__ partials,
+                                                                     float* __restrict__ means,
+                                                                     float* __restrict__ out_image,
+                                                                     int64_t* __restrict__ out_mask, int H, int W, int th,
+                                                                     int tw, int parts, int items) {
+    const int n = blockIdx.y;
+    const float* rec = params + (size_t)n * AUG_P;
+    const AugCrop o = aug_origin(rec, H, W);
+    const bool flip = rec[AUG_FLIP] != 0.f, ident = rec[AUG_IDENT] != 0.f;
+    const float m00 = rec[AUG_M], m01 = rec[AUG_M + 1], m02 = rec[AUG_M + 2], m10 = rec[AUG_M + 3], m11 = rec[AUG_M + 4],
+                m12 = rec[AUG_M + 5];
+    float mean_g = 0.f;
+    if (partials) {
+        double s = 0.0;
+        for (int p = 0; p < parts; ++p) s += (double)partials[(size_t)n * parts + p];
+        mean_g = (float)(s / (double)((size_t)th * tw));
+    }
+    if (means && blockIdx.x == 0 && threadIdx.x == 0) means[n] = mean_g;
+    const int tw4 = (tw + 3) >> 2;
+    for (int it = blockIdx.x * MEDT_THREADS + threadIdx.x; it < items; it += gridDim.x * MEDT_THREADS) {
+        const int i = it / tw4, j0 = (it - i * tw4) * 4;
+        float v[4][C];
+        int64_t lab[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = j0 + e;
+            int sx = j, sy = i;
+            bool inside = VEC4 || j < tw;
+            if (!ident) {
+                const float fx = m00 * (j + 0.5f) + m01 * (i + 0.5f) + m02, fy = m10 * (j + 0.5f) + m11 * (i + 0.5f) + m12;
+                inside = inside && fx >= 0.f && fx < (float)tw && fy >= 0.f && fy < (float)th;      // false for NaN
+                sx = inside ? (int)floorf(fx) : 0;
+                sy = inside ? (int)floorf(fy) : 0;
+            }
+            if (flip) sx = tw - 1 - sx;
+            const int y = min(max(o.cy + sy, 0), H - 1), x = min(max(o.cx + sx, 0), W - 1);
+            const size_t px = ((size_t)n * H + y) * W + x;
+            lab[e] = 0;
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[e][c] = 0.f;
+            if (inside) {
+                lab[e] = (int64_t)mask[px];
+#pragma unroll
+                for (int c = 0; c < C; ++c) v[e][c] = (float)image[px * C + c] / 255.f;
+                aug_jitter<C, false>(v[e], rec, mean_g);
+            }
+        }
+        int64_t* ml = out_mask + ((size_t)n * th + i) * tw + j0;
+        if (VEC4) {
+            AugLabel2 l01, l23;
+            l01.a = lab[0]; l01.b = lab[1]; l23.a = lab[2]; l23.b = lab[3];
+            reinterpret_cast<AugLabel2*>(ml)[0] = l01;
+            reinterpret_cast<AugLabel2*>(ml)[1] = l23;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (j0 + e < tw) ml[e] = lab[e];
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            float* dst = out_image + (((size_t)n * C + c) * th + i) * tw + j0;
+            if (VEC4) {
+                *reinterpret_cast<float4*>(dst) = make_float4(v[0][c], v[1][c], v[2][c], v[3][c]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (j0 + e < tw) dst[e] = v[e][c];
+            }
+        }
+    }
+}
+
+int augment_stats(const uint8_t* image, const float* params, float* workspace, int N, int H, int W, int C, int th, int tw,
+                  hipStream_t s) {
+    const int parts = augment_parts(th, tw);
+    if (C == 3)
+        hipLaunchKernelGGL((augment_stats_kernel<3>), dim3(parts, N), dim3(MEDT_THREADS), 0, s, image, params, workspace, H, W,
+                           th, tw, parts);
+    else
+        hipLaunchKernelGGL((augment_stats_kernel<1>), dim3(parts, N), dim3(MEDT_THREADS), 0, s, image, params, workspace, H, W,
+                           th, tw, parts);
+    return launch_status("augment_stats");
+}
+
+int augment_apply(const uint8_t* image, const uint8_t* mask, const float* params, float* workspace, float* out_image,
+                  int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, hipStream_t s) {
+    const int parts = augment_parts(th, tw), items = th * ((tw + 3) / 4);
+    const float* partials = (workspace && use_stats) ? workspace : nullptr;
+    float* means = workspace ? workspace + (size_t)N * parts : nullptr;
+    const dim3 grid((unsigned)min((items + MEDT_THREADS - 1) / MEDT_THREADS, 1024), N), block(MEDT_THREADS);
+    const bool vec = (tw % 4 == 0) && ((uintptr_t)out_image % 16 == 0) && ((uintptr_t)out_mask % 16 == 0);
+#define MEDT_AUG_LAUNCH(CC, VV)                                                                                            \
+    hipLaunchKernelGGL((augment_apply_kernel<CC, VV>), grid, block, 0, s, image, mask, params, partials, means, out_image, \
+                       out_mask, H, W, th, tw, parts, items)
+    if (C == 3) {
+        if (vec) MEDT_AUG_LAUNCH(3, true); else MEDT_AUG_LAUNCH(3, false);
+    } else {
+        if (vec) MEDT_AUG_LAUNCH(1, true); else MEDT_AUG_LAUNCH(1, false);
+    }
+#undef MEDT_AUG_LAUNCH
+    return launch_status("augment_apply");
 }
 
 }  // namespace medt

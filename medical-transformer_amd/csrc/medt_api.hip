@@ -965,4 +965,51 @@ int medt_window_blend(const float* win_logits, float* blended, uint8_t* mask, co
     return window_blend(win_logits, blended, mask, oy, ox, K, H, W, S, ny, nx, threshold, (hipStream_t)stream);
 }
 
+size_t medt_augment_param_floats(void) { return augment_param_floats(); }
+
+static bool augment_geometry_ok(const char* what, int N, int H, int W, int C, int th, int tw) {
+    if (N < 1 || H < 1 || W < 1 || th < 1 || tw < 1 || (C != 1 && C != 3)) {
+        set_error("%s: bad arguments (N %d, input %d x %d x %d, output %d x %d; 1 or 3 channels)", what, N, H, W, C, th, tw);
+        return false;
+    }
+    return true;
+}
+
+size_t medt_augment_workspace(int N, int th, int tw) {
+    if (N < 1 || th < 1 || tw < 1 || (size_t)th * tw >= ((size_t)1 << 31)) {
+        set_error("augment_workspace: bad arguments (N %d, output %d x %d)", N, th, tw);
+        return 0;
+    }
+    return (size_t)N * augment_parts(th, tw) + (size_t)N;
+}
+
+int medt_augment_stats(const uint8_t* image, const float* params, float* workspace, int N, int H, int W, int C, int th,
+                       int tw, void* stream) {
+    if (!augment_geometry_ok("augment_stats", N, H, W, C, th, tw)) return MEDT_EINVAL;
+    if (!image || !params || !workspace) {
+        set_error("augment_stats: null image, parameter table or workspace"); return MEDT_EINVAL;
+    }
+    if ((size_t)N * H * W * C >= ((size_t)1 << 31) || (size_t)N * C * th * tw >= ((size_t)1 << 31)) {
+        set_error("augment_stats: %d images of %d x %d x %d -> %d x %d: 2^31 elements or more", N, H, W, C, th, tw);
+        return MEDT_EUNSUPPORTED;
+    }
+    return augment_stats(image, params, workspace, N, H, W, C, th, tw, (hipStream_t)stream);
+}
+
+int medt_augment_apply(const uint8_t* image, const uint8_t* mask, const float* params, float* workspace, float* out_image,
+                       int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, void* stream) {
+    if (!augment_geometry_ok("augment_apply", N, H, W, C, th, tw)) return MEDT_EINVAL;
+    if (!image || !mask || !params || !out_image || !out_mask) {
+        set_error("augment_apply: null image, mask, parameter table or output"); return MEDT_EINVAL;
+    }
+    if (use_stats && !workspace) {
+        set_error("augment_apply: use_stats without the workspace medt_augment_stats filled"); return MEDT_EINVAL;
+    }
+    if ((size_t)N * H * W * C >= ((size_t)1 << 31) || (size_t)N * C * th * tw >= ((size_t)1 << 31)) {
+        set_error("augment_apply: %d images of %d x %d x %d -> %d x %d: 2^31 elements or more", N, H, W, C, th, tw);
+        return MEDT_EUNSUPPORTED;
+    }
+    return augment_apply(image, mask, params, workspace, out_image, out_mask, N, H, W, C, th, tw, use_stats, (hipStream_t)stream);
+}
+
 }  // extern "C"

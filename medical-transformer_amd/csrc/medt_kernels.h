@@ -122,6 +122,13 @@ int window_gather(const float* image, float* windows, const int32_t* oy, const i
                   int ny, int nx, hipStream_t s);
 int window_blend(const float* win, float* blended, uint8_t* mask, const int32_t* oy, const int32_t* ox, int K, int H, int W,
                  int S, int ny, int nx, float threshold, hipStream_t s);
+size_t augment_param_floats();
+int augment_parts(int th, int tw);                 // partial sums per image of augment_stats
+// workspace: N*augment_parts() partial sums, then N means (what the contrast slot of each record used)
+int augment_stats(const uint8_t* image, const float* params, float* workspace, int N, int H, int W, int C, int th, int tw,
+                  hipStream_t s);
+int augment_apply(const uint8_t* image, const uint8_t* mask, const float* params, float* workspace, float* out_image,
+                  int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, hipStream_t s);
 int logo_merge_fwd(const float* x, const float* yp, float* y, int N, int C, int S, int P, int G, hipStream_t s);
 int logo_merge_bwd(const float* dy, float* dx, float* dyp, int N, int C, int S, int P, int G, hipStream_t s);
 int ce_parts(size_t npix);

@@ -102,11 +102,12 @@ class ImageToImage2D(Dataset):
         else:
             mask = (mask > 127).astype(np.uint8)
         image, mask = correct_dims(image, mask)
-        image, mask = self.joint_transform(image, mask)
+        # (medt_amd.augment.RawJointTransform2D returns its parameter record behind the pair: it travels in front of the name)
+        image, mask, *extra = self.joint_transform(image, mask)
         if self.one_hot_mask:
             assert self.one_hot_mask > 0, "one_hot_mask must be nonnegative"
             mask = torch.zeros((self.one_hot_mask, mask.shape[1], mask.shape[2])).scatter_(0, mask.long(), 1)
-        return image, mask, name
+        return (image, mask, *extra, name)
 
 
 class Image2D(Dataset):
@@ -197,12 +198,14 @@ class DevicePrefetcher:
     own stream (train.py:90,130-135: num_workers=0, blocking `.to(device)`); at ~4 ms per MI355X step that
     serialises host decode + H2D with the GPU work.  Here a background thread pulls batches from the loader (same
     order, same np.random stream for the flips), stages them in reusable PINNED buffers and issues the H2D copies
-    on a dedicated copy stream; the consumer only waits on the copy's event.  Tensors past the first two entries of
-    a batch (file names ...) pass through untouched.  On a CPU device it degenerates to plain iteration.
+    on a dedicated copy stream; the consumer only waits on the copy's event.  Tensors past the first `stage` entries of
+    a batch (file names ...) pass through untouched; stage = 3 also carries the record table of the device-side
+    augmentation (medt_amd.augment) through the pinned ring and the copy stream.  On a CPU device it degenerates to plain
+    iteration.
     """
 
-    def __init__(self, loader, device, depth: int = 2):
-        self.loader, self.device, self.depth = loader, torch.device(device), max(1, depth)
+    def __init__(self, loader, device, depth: int = 2, stage: int = 2):
+        self.loader, self.device, self.depth, self.stage = loader, torch.device(device), max(1, depth), max(1, stage)
 
     def __len__(self):
         return len(self.loader)
@@ -250,7 +253,7 @@ class DevicePrefetcher:
                         return
                     out = list(batch)
                     with GPU_CAPTURE_LOCK, torch.cuda.stream(copy_stream):
-                        slots = [staged(t) for t in out[:2]]
+                        slots = [staged(t) for t in out[:self.stage]]
                         for i, slot in enumerate(slots):
                             out[i] = slot[0].to(self.device, non_blocking=True)
                         ev = torch.cuda.Event()
@@ -275,7 +278,7 @@ class DevicePrefetcher:
                 out, ev = item
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(ev)
-                for t in out[:2]:
+                for t in out[:self.stage]:
                     t.record_stream(cur)
                 yield tuple(out)
         finally:

@@ -552,3 +552,68 @@ def window_blend(win_logits, oy, ox, H, W, threshold=0.5, want_logits=True, want
     L.check(L.lib().medt_window_blend(win_logits.data_ptr(), L.ptr(blended), L.ptr(mask), oy.data_ptr(), ox.data_ptr(), K,
                                       H, W, S, oy.numel(), ox.numel(), float(threshold), _stream()), "medt_window_blend")
     return blended, mask
+
+
+# --------------------------------------------------------------------------- #
+# joint augmentation of uint8 batches (medt_amd.augment)
+# --------------------------------------------------------------------------- #
+AUG_CONTRAST = 2.0          # operation code of a contrast slot (include/medt_abi.h)
+
+
+def augment_param_floats():
+    return int(L.lib().medt_augment_param_floats())
+
+
+def augment_workspace(N, size):
+    """Floats of workspace for N images of output size (th, tw): the partial sums of the contrast mean, then the N means."""
+    n = int(L.lib().medt_augment_workspace(int(N), int(size[0]), int(size[1])))
+    if n == 0:
+        raise L.MedtError(f"medt_augment_workspace: {L.lib().medt_last_error().decode()}")
+    return n
+
+
+def augment_batch(img_u8, mask_u8, params, size, out=None, workspace=None, host_params=None):
+    """uint8 (N,H,W,C) images + uint8 (N,H,W) masks -> (float32 (N,C,th,tw) in [0,1], int64 (N,th,tw)): crop, flip, colour
+    jitter and affine map of each image by its record of the float32 (N,P) device table `params` (medt_amd.augment.draw_record).
+    size = (th, tw).  out: an (image, mask) pair to write into (contiguous; a view that is not 16-byte aligned takes the
+    kernels' element stores).  workspace: augment_workspace() floats; after the call its last N floats hold the means the
+    contrast operations used.  host_params: the table as a CPU tensor, when the caller has it (the prefetcher does): the origin
+    check and the choice of launches read it instead of copying `params` back, which waits for the device."""
+    if img_u8.dtype != torch.uint8 or mask_u8.dtype != torch.uint8:
+        raise L.MedtError("augment_batch: uint8 images and masks expected")
+    _require_device(params)                # (a float32 device tensor; images and masks must live where the table does, below)
+    if img_u8.dim() != 4 or mask_u8.dim() != 3 or tuple(mask_u8.shape) != tuple(img_u8.shape[:3]):
+        raise L.MedtError("augment_batch: an (N,H,W,C) image batch and its (N,H,W) masks expected")
+    N, H, W, Cc = img_u8.shape
+    th, tw = int(size[0]), int(size[1])
+    P = augment_param_floats()
+    if (params.dtype != torch.float32 or params.dim() != 2 or tuple(params.shape) != (N, P) or not params.is_contiguous()
+            or params.device != img_u8.device or mask_u8.device != img_u8.device):
+        raise L.MedtError(f"augment_batch: a contiguous float32 ({N},{P}) parameter table on the images' device expected")
+    host = params.cpu() if host_params is None else host_params
+    if tuple(host.shape) != (N, P):
+        raise L.MedtError(f"augment_batch: host_params must be the ({N},{P}) table")
+    cy, cx = host[:, 0], host[:, 1]
+    if not (bool((cy >= 0).all()) and bool((cx >= 0).all()) and bool((cy + th <= H).all()) and bool((cx + tw <= W).all())):
+        raise L.MedtError(f"augment_batch: a crop origin puts the {th} x {tw} window outside the {H} x {W} image")
+    use_stats = bool((host[:, 10:14] == AUG_CONTRAST).any())
+    img_u8, mask_u8 = img_u8.contiguous(), mask_u8.contiguous()
+    if out is None:
+        out = (torch.empty((N, Cc, th, tw), device=img_u8.device, dtype=torch.float32),
+               torch.empty((N, th, tw), device=img_u8.device, dtype=torch.int64))
+    oi, om = out
+    if (oi.dtype != torch.float32 or om.dtype != torch.int64 or tuple(oi.shape) != (N, Cc, th, tw) or tuple(om.shape) != (N, th, tw)
+            or not oi.is_contiguous() or not om.is_contiguous() or oi.device != img_u8.device or om.device != img_u8.device):
+        raise L.MedtError("augment_batch: out must be contiguous float32 (N,C,th,tw) and int64 (N,th,tw) tensors on the images' device")
+    if workspace is None and use_stats:
+        workspace = torch.empty(augment_workspace(N, (th, tw)), device=img_u8.device, dtype=torch.float32)
+    if workspace is not None and (workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != img_u8.device
+                                  or workspace.numel() < augment_workspace(N, (th, tw))):
+        raise L.MedtError("augment_batch: workspace must hold augment_workspace() float32 on the images' device")
+    lib = L.lib()
+    if use_stats:
+        L.check(lib.medt_augment_stats(img_u8.data_ptr(), params.data_ptr(), workspace.data_ptr(), N, H, W, Cc, th, tw, _stream()),
+                "medt_augment_stats")
+    L.check(lib.medt_augment_apply(img_u8.data_ptr(), mask_u8.data_ptr(), params.data_ptr(), L.ptr(workspace), oi.data_ptr(),
+                                   om.data_ptr(), N, H, W, Cc, th, tw, int(use_stats), _stream()), "medt_augment_apply")
+    return oi, om
