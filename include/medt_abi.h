@@ -35,7 +35,9 @@ extern "C" {
 #endif
 
 /* 11: medt_seg_loss_*.  The medt_augment_* entry points were added under the same number: additions only, nothing that
- * version 11 declared was removed or changed, so a caller built against the earlier header keeps working. */
+ * version 11 declared was removed or changed, so a caller built against the earlier header keeps working.  The medt_edt_*
+ * entry points were added under the same number: additions only, nothing that version 11 declared was removed or changed,
+ * so a caller built against the earlier header keeps working. */
 #define MEDT_ABI_VERSION 11
 
 #define MEDT_OK            0
@@ -423,6 +425,34 @@ int medt_augment_stats(const uint8_t* image, const float* params, float* workspa
                        int tw, void* stream);
 int medt_augment_apply(const uint8_t* image, const uint8_t* mask, const float* params, float* workspace, float* out_image,
                        int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, void* stream);
+
+/* Exact squared Euclidean distance transform of binary masks on the device, in two passes -- the building block of the
+ * surface-distance scores (metrics.surface_scores: Hausdorff distance, its 95th percentile, average symmetric surface
+ * distance; not in the reference, whose users take them from SciPy / MedPy on the host).
+ *   edt_sq(F)[y,x] = min over (y',x') in F of (y-y')^2 + (x-x')^2 = distance_transform_edt(~F)**2, exactly, as int32;
+ *   every pixel of an image whose F is empty holds MEDT_EDT_NONE.
+ * The foreground of a mask is mask != 0.  Its BORDER is the foreground pixels with at least one 4-neighbour outside the
+ * foreground, pixels outside the image counting as outside (A & ~binary_erosion(A, cross, border_value=0), MedPy's
+ * surface): a foreground pixel on the image edge is always border.
+ *
+ * medt_edt_cols: mask (N,H,W) uint8 -> g2 (N,H,W) int32, g2[y,x] = (y-y')^2 for the feature pixel (y',x) of column x nearest
+ * to y, MEDT_EDT_NONE when the column has none.  border_mode == 0: the features are the foreground; != 0: its border,
+ * derived from the mask on the fly (never stored).  One work-item per (image, column); g2 is scratch of the pass as well
+ * (written by the downward sweep, read back and overwritten by the upward one), so it must not alias mask.
+ * medt_edt_rows: g2 (N,H,W) int32 from medt_edt_cols -> d2 (N,H,W) int32, d2[y,x] = min over x' of (x-x')^2 + g2[y,x'],
+ * MEDT_EDT_NONE when the image has no feature pixel.  select == NULL: every pixel.  select (N,H,W) uint8: only the border
+ * pixels of select != 0 receive the value, every other pixel receives -1 (the distances from the surface of one mask to the
+ * surface of another in one map).  One workgroup per (image, row), the row of g2 in LDS; d2 must not alias g2.
+ * cols(mask, 0) + rows(select NULL) is edt_sq of the foreground; cols(b, 1) + rows(select a) the surface distances a -> b.
+ *
+ * Integers throughout, no atomics: exact, and bit-identical from run to run.  The sentinel never enters a sum.  16-byte
+ * accesses when W % 4 == 0 and the pointers are aligned (g2, d2 to 16 bytes, mask to 4), element accesses otherwise.
+ * 1 <= H, W <= MEDT_EDT_MAX_DIM and N*H*W below 2^31 (MEDT_EUNSUPPORTED beyond, checked on the host before any launch).
+ * The caller owns all memory. */
+#define MEDT_EDT_NONE    2147483647   /* INT32_MAX: no feature pixel in the image (d2) / in the column (g2) */
+#define MEDT_EDT_MAX_DIM 4096
+int medt_edt_cols(const uint8_t* mask, int32_t* g2, int N, int H, int W, int border_mode, void* stream);
+int medt_edt_rows(const int32_t* g2, const uint8_t* select, int32_t* d2, int N, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

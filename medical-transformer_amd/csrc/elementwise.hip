@@ -6,6 +6,7 @@
 //   Adam with coupled L2 weight decay over a flat buffer     (train.py:111-112,161)
 //   sliding-window gather / blend for images larger than the network input (not in the reference)
 //   joint augmentation of uint8 batches: crop, flip, colour jitter, affine (utils.py:70-98)
+//   exact squared Euclidean distance transform of uint8 masks, for the surface-distance scores (not in the reference)
 // All HBM-bound: one element per lane, NCHW rows coalesced, per-channel constants via scalar loads.
 #include "medt_kernels.h"
 #include <stdint.h>
@@ -1393,6 +1394,213 @@ int augment_apply(const uint8_t* image, const uint8_t* mask, const float* params
     }
 #undef MEDT_AUG_LAUNCH
     return launch_status("augment_apply");
+}
+
+// --------------------------------------------------------------------------- //
+// Exact squared Euclidean distance transform of uint8 masks (N,H,W) -> int32 (N,H,W), for the surface-distance scores
+// (metrics.surface_scores: Hausdorff distance, its 95th percentile, average symmetric surface distance; not in the reference).
+//   d2[y,x] = min over the feature pixels (y',x') of (y-y')^2 + (x-x')^2      MEDT_EDT_NONE where the image has none
+// Feature set: mask != 0, or (border mode) the BORDER of mask != 0 -- the foreground pixels with a 4-neighbour outside the
+// foreground, pixels outside the image counting as outside (MedPy's surface, A & ~binary_erosion(A, cross)).  Separable:
+//   column pass  g2[y,x] = (distance along the column x to its nearest feature pixel)^2, or MEDT_EDT_NONE
+//   row pass     d2[y,x] = min over x' of (x-x')^2 + g2[y,x']
+// All integers (g <= 4095, so every sum stays below 2^26): the result is exact, and with no atomics the same on every run.
+// The sentinel never enters a sum: the column pass tests for it before counting on, the row pass stages EDT_FAR in its place.
+// --------------------------------------------------------------------------- //
+constexpr int EDT_FAR = 1 << 30;              // what the row pass holds in LDS for MEDT_EDT_NONE: EDT_FAR + 4095^2 < 2^31
+constexpr int EDT_ROWS = 8;                   // rows of a column whose loads the column pass issues together
+
+struct alignas(16) EdtQuad {
+    int32_t v[4];
+};
+
+// bit e: column e of the work-item's CPT columns is foreground.  (Flags are kept as bits of one word per row: arrays of
+// bool would each live in a pair of scalar registers as a lane mask.)
+template <int CPT>
+__device__ __forceinline__ uint32_t edt_load_set(const uint8_t* __restrict__ p) {
+    if (CPT == 4) {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
+        uint32_t f = 0;
+#pragma unroll
+        for (int e = 0; e < CPT; ++e) f |= ((w >> (8 * e)) & 255u) ? 1u << e : 0u;
+        return f;
+    }
+    return p[0] ? 1u : 0u;
+}
+template <int CPT>
+__device__ __forceinline__ void edt_load_dist(const int32_t* __restrict__ p, int (&a)[CPT]) {
+    if (CPT == 4) {
+        const EdtQuad q = *reinterpret_cast<const EdtQuad*>(p);
+#pragma unroll
+        for (int e = 0; e < CPT; ++e) a[e] = q.v[e];
+    } else {
+        a[0] = p[0];
+    }
+}
+template <int CPT>
+__device__ __forceinline__ void edt_store_dist(int32_t* __restrict__ p, const int (&a)[CPT]) {
+    if (CPT == 4) {
+        EdtQuad q;
+#pragma unroll
+        for (int e = 0; e < CPT; ++e) q.v[e] = a[e];
+        *reinterpret_cast<EdtQuad*>(p) = q;
+    } else {
+        p[0] = a[0];
+    }
+}
+
+// A work-item owns CPT neighbouring columns of one image (4 with 16-byte stores, else 1), so neighbouring lanes touch
+// neighbouring x.  Sweep down: the distance to the nearest feature pixel at or above, written to g2; sweep up: the one
+// below, the smaller of the two squared.  The sweeps are serial in y, so each issues the loads of EDT_ROWS rows in front of
+// the arithmetic.  Border mode derives the feature set from the mask as it goes (the rows y-1, y, y+1 of the own columns
+// and one byte to either side); the border is never stored.
+template <int CPT, bool BORDER>
+__global__ __launch_bounds__(MEDT_THREADS) void edt_cols_kernel(const uint8_t* __restrict__ mask, int32_t* __restrict__ g2,
+                                                                int H, int W, int bpi) {
+    const int n = blockIdx.x / bpi;
+    const int x0 = ((blockIdx.x - n * bpi) * blockDim.x + threadIdx.x) * CPT;
+    if (x0 >= W) return;
+    const uint8_t* m = mask + (size_t)n * H * W + x0;
+    int32_t* g = g2 + (size_t)n * H * W + x0;
+    constexpr uint32_t OWN = (1u << CPT) - 1u;
+    int dist[CPT];
+    uint32_t up = 0;                            // BORDER: the own columns of the row above the chunk (outside the image: 0)
+#pragma unroll
+    for (int e = 0; e < CPT; ++e) dist[e] = MEDT_EDT_NONE;
+    for (int yb = 0; yb < H; yb += EDT_ROWS) {
+        uint32_t c[EDT_ROWS + 1], side[EDT_ROWS];      // side: bit 0 the pixel left of the own columns, bit 1 the one right of them
+#pragma unroll
+        for (int r = 0; r <= EDT_ROWS; ++r) {
+            const int y = yb + r;
+            c[r] = 0;
+            if (r < EDT_ROWS) side[r] = 0;
+            if (y < H && (BORDER || r < EDT_ROWS)) {
+                const uint8_t* row = m + (size_t)y * W;
+                c[r] = edt_load_set<CPT>(row);
+                if (BORDER && r < EDT_ROWS) {
+                    if (x0 > 0 && row[-1] != 0) side[r] |= 1u;
+                    if (x0 + CPT < W && row[CPT] != 0) side[r] |= 2u;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < EDT_ROWS; ++r) {
+            const int y = yb + r;
+            if (y >= H) break;
+            uint32_t feat = c[r];
+            if (BORDER) {
+                const uint32_t above = r ? c[r ? r - 1 : 0] : up;
+                const uint32_t left = ((c[r] << 1) | (side[r] & 1u)) & OWN, right = (c[r] >> 1) | ((side[r] >> 1) << (CPT - 1));
+                feat &= ~(above & c[r + 1] & left & right);
+            }
+#pragma unroll
+            for (int e = 0; e < CPT; ++e)
+                dist[e] = ((feat >> e) & 1u) ? 0 : (dist[e] == MEDT_EDT_NONE ? MEDT_EDT_NONE : dist[e] + 1);
+            edt_store_dist<CPT>(g + (size_t)y * W, dist);
+        }
+        up = c[EDT_ROWS - 1];
+    }
+#pragma unroll
+    for (int e = 0; e < CPT; ++e) dist[e] = MEDT_EDT_NONE;
+    for (int yb = H - 1; yb >= 0; yb -= EDT_ROWS) {
+        int a[EDT_ROWS][CPT];
+#pragma unroll
+        for (int r = 0; r < EDT_ROWS; ++r)
+            if (yb - r >= 0) edt_load_dist<CPT>(g + (size_t)(yb - r) * W, a[r]);
+#pragma unroll
+        for (int r = 0; r < EDT_ROWS; ++r) {
+            const int y = yb - r;
+            if (y < 0) break;
+#pragma unroll
+            for (int e = 0; e < CPT; ++e) {
+                dist[e] = a[r][e] == 0 ? 0 : (dist[e] == MEDT_EDT_NONE ? MEDT_EDT_NONE : dist[e] + 1);
+                const int d = min(a[r][e], dist[e]);
+                a[r][e] = d == MEDT_EDT_NONE ? MEDT_EDT_NONE : d * d;
+            }
+            edt_store_dist<CPT>(g + (size_t)y * W, a[r]);
+        }
+    }
+}
+
+static inline unsigned edt_threads(int items) { return (unsigned)min(max((items + 63) / 64 * 64, 64), MEDT_THREADS); }
+
+int edt_cols(const uint8_t* mask, int32_t* g2, int N, int H, int W, int border_mode, hipStream_t s) {
+    const bool vec = (W % 4 == 0) && ((uintptr_t)mask % 4 == 0) && ((uintptr_t)g2 % 16 == 0);
+    const int items = vec ? W / 4 : W;
+    const unsigned threads = edt_threads(items);
+    const int bpi = cdiv(items, (int)threads);
+#define MEDT_EDT_COLS(CPT, BB) \
+    hipLaunchKernelGGL((edt_cols_kernel<CPT, BB>), dim3((unsigned)N * bpi), dim3(threads), 0, s, mask, g2, H, W, bpi)
+    if (vec) {
+        if (border_mode) MEDT_EDT_COLS(4, true); else MEDT_EDT_COLS(4, false);
+    } else {
+        if (border_mode) MEDT_EDT_COLS(1, true); else MEDT_EDT_COLS(1, false);
+    }
+#undef MEDT_EDT_COLS
+    return launch_status("edt_cols");
+}
+
+// One workgroup per (image, row): the row of g2 in LDS; a work-item owns the pixels x = tid, tid + threads, ... (neighbouring
+// lanes read neighbouring LDS words at every step of the search) and walks outwards from x, both sides at once, until
+// (x-x')^2 alone reaches the best value so far.  SELECT: only the border pixels of `select` are searched, the others
+// receive -1.  VEC4: 16-byte loads of g2, and the results go through LDS to leave as 16-byte stores.
+template <bool VEC4, bool SELECT>
+__global__ __launch_bounds__(MEDT_THREADS) void edt_rows_kernel(const int32_t* __restrict__ g2,
+                                                                const uint8_t* __restrict__ select, int32_t* __restrict__ d2,
+                                                                int H, int W) {
+    MEDT_STATIC_SHARED EdtQuad gq[MEDT_EDT_MAX_DIM / 4], oq[MEDT_EDT_MAX_DIM / 4];
+    int32_t* gs = reinterpret_cast<int32_t*>(gq);
+    int32_t* os = reinterpret_cast<int32_t*>(oq);
+    const int n = blockIdx.x / H, y = blockIdx.x - n * H, tid = threadIdx.x, T = blockDim.x;
+    const size_t row = ((size_t)n * H + y) * W;
+    if (VEC4) {
+        for (int i = tid; i < W / 4; i += T) {
+            EdtQuad q = reinterpret_cast<const EdtQuad*>(g2 + row)[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) q.v[e] = min(q.v[e], EDT_FAR);
+            gq[i] = q;
+        }
+    } else {
+        for (int x = tid; x < W; x += T) gs[x] = min(g2[row + x], EDT_FAR);
+    }
+    __syncthreads();
+    for (int x = tid; x < W; x += T) {
+        bool wanted = true;
+        if (SELECT) {
+            const uint8_t* c = select + row + x;
+            wanted = c[0] != 0 && (x == 0 || x == W - 1 || y == 0 || y == H - 1 || c[-1] == 0 || c[1] == 0 || c[-W] == 0 || c[W] == 0);
+        }
+        int best = -1;
+        if (wanted) {
+            best = gs[x];
+            const int reach = max(x, W - 1 - x);
+            for (int d = 1; d <= reach; ++d) {
+                const int dd = d * d;
+                if (dd >= best) break;
+                if (x - d >= 0) best = min(best, gs[x - d] + dd);
+                if (x + d < W) best = min(best, gs[x + d] + dd);
+            }
+            if (best >= EDT_FAR) best = MEDT_EDT_NONE;
+        }
+        if (VEC4) os[x] = best; else d2[row + x] = best;
+    }
+    if (VEC4) {
+        __syncthreads();
+        for (int i = tid; i < W / 4; i += T) reinterpret_cast<EdtQuad*>(d2 + row)[i] = oq[i];
+    }
+}
+
+int edt_rows(const int32_t* g2, const uint8_t* select, int32_t* d2, int N, int H, int W, hipStream_t s) {
+    const bool vec = (W % 4 == 0) && ((uintptr_t)g2 % 16 == 0) && ((uintptr_t)d2 % 16 == 0);
+    const dim3 grid((unsigned)N * H), block(edt_threads(W));
+#define MEDT_EDT_ROWS(VV, SS) hipLaunchKernelGGL((edt_rows_kernel<VV, SS>), grid, block, 0, s, g2, select, d2, H, W)
+    if (vec) {
+        if (select) MEDT_EDT_ROWS(true, true); else MEDT_EDT_ROWS(true, false);
+    } else {
+        if (select) MEDT_EDT_ROWS(false, true); else MEDT_EDT_ROWS(false, false);
+    }
+#undef MEDT_EDT_ROWS
+    return launch_status("edt_rows");
 }
 
 }  // namespace medt

@@ -1012,4 +1012,29 @@ int medt_augment_apply(const uint8_t* image, const uint8_t* mask, const float* p
     return augment_apply(image, mask, params, workspace, out_image, out_mask, N, H, W, C, th, tw, use_stats, (hipStream_t)stream);
 }
 
+static int edt_geometry(const char* what, int N, int H, int W) {
+    if (N < 1 || H < 1 || W < 1) {
+        set_error("%s: bad arguments (%d images of %d x %d)", what, N, H, W); return MEDT_EINVAL;
+    }
+    if (H > MEDT_EDT_MAX_DIM || W > MEDT_EDT_MAX_DIM) {
+        set_error("%s: %d x %d maps: at most %d pixels per side", what, H, W, MEDT_EDT_MAX_DIM); return MEDT_EUNSUPPORTED;
+    }
+    if ((size_t)N * H * W >= ((size_t)1 << 31)) {
+        set_error("%s: %d maps of %d x %d: 2^31 elements or more", what, N, H, W); return MEDT_EUNSUPPORTED;
+    }
+    return MEDT_OK;
+}
+
+int medt_edt_cols(const uint8_t* mask, int32_t* g2, int N, int H, int W, int border_mode, void* stream) {
+    if (const int rc = edt_geometry("edt_cols", N, H, W)) return rc;
+    if (!mask || !g2) { set_error("edt_cols: null mask or g2"); return MEDT_EINVAL; }
+    return edt_cols(mask, g2, N, H, W, border_mode, (hipStream_t)stream);
+}
+
+int medt_edt_rows(const int32_t* g2, const uint8_t* select, int32_t* d2, int N, int H, int W, void* stream) {
+    if (const int rc = edt_geometry("edt_rows", N, H, W)) return rc;
+    if (!g2 || !d2 || g2 == d2) { set_error("edt_rows: null g2 or d2, or d2 is g2"); return MEDT_EINVAL; }
+    return edt_rows(g2, select, d2, N, H, W, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -617,3 +617,58 @@ def augment_batch(img_u8, mask_u8, params, size, out=None, workspace=None, host_
     L.check(lib.medt_augment_apply(img_u8.data_ptr(), mask_u8.data_ptr(), params.data_ptr(), L.ptr(workspace), oi.data_ptr(),
                                    om.data_ptr(), N, H, W, Cc, th, tw, int(use_stats), _stream()), "medt_augment_apply")
     return oi, om
+
+
+# --------------------------------------------------------------------------- #
+# exact squared Euclidean distance transform (metrics.surface_scores)
+# --------------------------------------------------------------------------- #
+EDT_NONE = 2 ** 31 - 1      # MEDT_EDT_NONE (include/medt_abi.h): what an image without a feature pixel holds everywhere
+
+
+def _edt_masks(what, *masks):
+    """uint8 (N,H,W) or (H,W) masks of one shape on one device -> contiguous (N,H,W) views."""
+    m0 = masks[0]
+    _require_device(m0.new_empty(0, dtype=torch.float32))          # (the device check; the masks themselves are uint8)
+    for m in masks:
+        if m.dtype != torch.uint8 or m.dim() not in (2, 3) or m.shape != m0.shape or m.device != m0.device:
+            raise L.MedtError(f"{what}: uint8 (N,H,W) or (H,W) masks of one shape on one device expected")
+    if m0.numel() == 0:
+        raise L.MedtError(f"{what}: empty mask")
+    return [m.contiguous().reshape(-1, *m.shape[-2:]) for m in masks]
+
+
+def _edt_out(what, out, like):
+    if out is None:
+        return torch.empty(like.shape, device=like.device, dtype=torch.int32)
+    if out.dtype != torch.int32 or tuple(out.shape) != tuple(like.shape) or not out.is_contiguous() or out.device != like.device:
+        raise L.MedtError(f"{what}: out must be a contiguous int32 tensor of the masks' shape on their device")
+    return out
+
+
+def edt_sq(mask, border=False, out=None):
+    """uint8 (N,H,W) or (H,W) mask -> int32 of the same shape: the exact squared Euclidean distance of every pixel to the
+    nearest pixel of mask != 0 (`distance_transform_edt(mask == 0) ** 2`), or with border=True to the nearest BORDER pixel of
+    mask != 0 (a foreground pixel with a 4-neighbour outside the foreground or outside the image).  EDT_NONE everywhere in an
+    image without foreground.  At most 4096 pixels per side.  out: an int32 tensor to write into (a view that is not
+    16-byte aligned takes the kernels' element accesses)."""
+    (m,) = _edt_masks("edt_sq", mask)
+    N, H, W = m.shape
+    d2 = _edt_out("edt_sq", out, mask)
+    g2 = torch.empty(m.shape, device=m.device, dtype=torch.int32)
+    lib = L.lib()
+    L.check(lib.medt_edt_cols(m.data_ptr(), g2.data_ptr(), N, H, W, int(bool(border)), _stream()), "medt_edt_cols")
+    L.check(lib.medt_edt_rows(g2.data_ptr(), None, d2.data_ptr(), N, H, W, _stream()), "medt_edt_rows")
+    return d2
+
+
+def surface_d2(a, b, out=None):
+    """Two uint8 masks (N,H,W) or (H,W) -> int32 of the same shape: at the border pixels of a != 0 the squared distance to the
+    nearest border pixel of b != 0 (EDT_NONE when b has none), -1 at every other pixel.  The border of b is never stored."""
+    ma, mb = _edt_masks("surface_d2", a, b)
+    N, H, W = ma.shape
+    d2 = _edt_out("surface_d2", out, a)
+    g2 = torch.empty(ma.shape, device=ma.device, dtype=torch.int32)
+    lib = L.lib()
+    L.check(lib.medt_edt_cols(mb.data_ptr(), g2.data_ptr(), N, H, W, 1, _stream()), "medt_edt_cols")
+    L.check(lib.medt_edt_rows(g2.data_ptr(), ma.data_ptr(), d2.data_ptr(), N, H, W, _stream()), "medt_edt_rows")
+    return d2

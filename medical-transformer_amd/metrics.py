@@ -89,3 +89,41 @@ def segmentation_scores(counts):
     pa = tp / (tp + fn).clamp_min(1)
     f1[one], iou[one], pa[one] = 1.0, 1.0, 1.0
     return f1, iou, pa
+
+
+def surface_scores(pred_mask, target_mask):
+    """Per-image surface-distance scores of two uint8 masks (N,H,W) or (H,W) on the device, foreground = mask != 0 (the
+    {0,255} masks test.py writes; for a label map pass `(target > 0).to(torch.uint8)`):
+      hd    Hausdorff distance: the largest distance from a border pixel of one mask to the border of the other
+      hd95  the 95th percentile (linear interpolation, numpy.percentile) of those distances, both directions pooled
+      assd  average symmetric surface distance, (mean A->B + mean B->A) / 2
+    in pixels, with MedPy's surface (a foreground pixel with a 4-neighbour outside the foreground or the image).
+    -> {"hd", "hd95", "assd": float64 (N,), "valid": bool (N,)} on the CPU.  An image whose prediction or target has no
+    foreground has valid False and NaN scores (MedPy raises there; an evaluation loop must not).
+
+    The distances are exact integers squared (medt_amd.ops.surface_d2, two calls); they are sorted on the device, the square
+    roots are taken in float64 there, and hd is the float64 root of the largest integer."""
+    import math
+    from medt_amd import ops
+    d_ab = ops.surface_d2(pred_mask, target_mask)
+    d_ba = ops.surface_d2(target_mask, pred_mask)
+    H, W = d_ab.shape[-2:]
+    d_ab, d_ba = d_ab.reshape(-1, H * W), d_ba.reshape(-1, H * W)
+    N = d_ab.shape[0]
+    has = ((pred_mask.reshape(N, -1) != 0).any(dim=1) & (target_mask.reshape(N, -1) != 0).any(dim=1)).cpu()
+    out = {k: torch.full((N,), float("nan"), dtype=torch.float64) for k in ("hd", "hd95", "assd")}
+    out["valid"] = has.clone()
+    for n in range(N):
+        if not bool(has[n]):
+            continue
+        ab, ba = d_ab[n][d_ab[n] >= 0], d_ba[n][d_ba[n] >= 0]
+        both, _ = torch.sort(torch.cat([ab, ba]))
+        root = both.double().sqrt()
+        k = both.numel()
+        pos = 0.95 * (k - 1)
+        lo = int(math.floor(pos))
+        hi = min(lo + 1, k - 1)
+        out["hd"][n] = math.sqrt(float(int(both[-1])))
+        out["hd95"][n] = float(root[lo]) + (float(root[hi]) - float(root[lo])) * (pos - lo)
+        out["assd"][n] = 0.5 * (float(ab.double().sqrt().mean()) + float(ba.double().sqrt().mean()))
+    return out

@@ -2,7 +2,8 @@
 """Drop-in for the reference's test.py (reference test.py:28-146): same flags; loads a checkpoint written by
 train.py (with or without DataParallel's "module." prefix), runs the network in eval mode and writes the
 thresholded channel-1 prediction of every validation image as <direc>/<filename>.  The reference reads an
-undefined args.aug (test.py:62) and dies; here the flag exists and is ignored."""
+undefined args.aug (test.py:62) and dies; here the flag exists and is ignored.  --surface on adds the surface-distance scores
+(HD, HD95, ASSD) of the written masks behind the F1 / mIoU / PA line."""
 import argparse
 import os
 
@@ -44,6 +45,11 @@ parser.add_argument('--window', default='off', choices=['off', 'on'],
                          'device, the windows run --gather per replay and their logits are blended into a map of the '
                          "image's own size (medt_amd.window.WindowInfer)")
 parser.add_argument('--window_stride', type=int, default=None, help='window step in pixels with --window on (default: imgsize / 2)')
+parser.add_argument('--surface', default='off', choices=['off', 'on'],
+                    help='(not in the reference) on: a second score line with the surface-distance scores of the written masks '
+                         'against the label maps -- Hausdorff distance, its 95th percentile and the average symmetric surface '
+                         'distance, in pixels, means over the images whose mask and label map both have foreground '
+                         '(metrics.surface_scores: distance transforms on the device)')
 
 
 def main():
@@ -71,6 +77,7 @@ def main():
     fulldir = args.direc + "/"
     os.makedirs(fulldir, exist_ok=True)
     scores = []
+    surface = [] if args.surface == "on" else None     # per-batch metrics.surface_scores of (mask, target > 0), eager, behind the replay
     # forward + the device-side counts as ONE replayed hipGraph per image shape (medt_amd.trainer.InferStep): an eager
     # forward is ~110 dependent launches issued from Python and is host-bound
     infer = InferStep(model)
@@ -83,6 +90,9 @@ def main():
         ys = torch.cat([it[1].long().reshape(1, *it[0].shape[2:]) for it in items] + [items[-1][1].long().reshape(1, *items[-1][0].shape[2:])] * (gather - len(items))).to(device)
         y_out, counts = infer(xs, ys)
         scores.append(counts[:len(items)].clone())
+        if surface is not None:                        # the mask the PNG holds (same comparison, on the device) against target > 0
+            surface.append(metrics.surface_scores((y_out[:len(items), 1] >= 0.5).to(torch.uint8) * 255,
+                                                  (ys[:len(items)] > 0).to(torch.uint8)))
         yHaT = (y_out[:len(items)].detach().cpu().numpy() >= 0.5).astype(np.uint8) * 255
         for k, it in enumerate(items):
             imwrite(fulldir + it[2], yHaT[k, 1, :, :])
@@ -96,8 +106,11 @@ def main():
         winfer = WindowInfer(model, args.imgsize, gather=gather, stride=args.window_stride)
         for batch_idx, (X_batch, y_batch, *rest) in enumerate(valloader):
             image_filename = rest[0][0] if isinstance(rest[0][0], str) else '%s.png' % str(batch_idx + 1).zfill(3)
-            _, mask, counts = winfer(X_batch.to(device), y_batch.long().reshape(1, *X_batch.shape[2:]).to(device))
+            target = y_batch.long().reshape(1, *X_batch.shape[2:]).to(device)
+            _, mask, counts = winfer(X_batch.to(device), target)
             scores.append(counts)
+            if surface is not None:
+                surface.append(metrics.surface_scores(mask.unsqueeze(0), (target > 0).to(torch.uint8)))
             imwrite(fulldir + image_filename, mask.cpu().numpy())
         valloader = ()
     for batch_idx, (X_batch, y_batch, *rest) in enumerate(valloader):
@@ -115,6 +128,11 @@ def main():
         f1, iou, pa = metrics.segmentation_scores(torch.cat(scores))
         print("images {}  F1 {:.4f}  mIoU {:.4f}  PA {:.4f}".format(len(f1), f1.mean().item(), iou.mean().item(),
                                                                    pa.mean().item()))
+    if surface:
+        valid = torch.cat([s["valid"] for s in surface])
+        hd, hd95, assd = (torch.cat([s[k] for s in surface])[valid] for k in ("hd", "hd95", "assd"))
+        print("surface images {}/{}  HD {:.4f}  HD95 {:.4f}  ASSD {:.4f}".format(
+            int(valid.sum()), len(valid), *(v.mean().item() if len(v) else float("nan") for v in (hd, hd95, assd))))
 
 
 if __name__ == "__main__":
