@@ -37,7 +37,9 @@ extern "C" {
 /* 11: medt_seg_loss_*.  The medt_augment_* entry points were added under the same number: additions only, nothing that
  * version 11 declared was removed or changed, so a caller built against the earlier header keeps working.  The medt_edt_*
  * entry points were added under the same number: additions only, nothing that version 11 declared was removed or changed,
- * so a caller built against the earlier header keeps working. */
+ * so a caller built against the earlier header keeps working.  The medt_label_* entry points were added under the same
+ * number: additions only, nothing that version 11 declared was removed or changed, so a caller built against the earlier
+ * header keeps working. */
 #define MEDT_ABI_VERSION 11
 
 #define MEDT_OK            0
@@ -453,6 +455,46 @@ int medt_augment_apply(const uint8_t* image, const uint8_t* mask, const float* p
 #define MEDT_EDT_MAX_DIM 4096
 int medt_edt_cols(const uint8_t* mask, int32_t* g2, int N, int H, int W, int border_mode, void* stream);
 int medt_edt_rows(const int32_t* g2, const uint8_t* select, int32_t* d2, int N, int H, int W, void* stream);
+
+/* Connected-component labelling of binary masks on the device, the per-component tables and a table-driven select pass -- the
+ * building blocks of the object-level scores (metrics.object_scores: GlaS object F1 / Dice, AJI, PQ) and of the two mask
+ * clean-ups "drop objects below an area" and "fill holes" (not in the reference, whose users call scipy.ndimage.label or
+ * MATLAB's bwlabel on the host).
+ *
+ * medt_label_components: mask (N,H,W) uint8 -> labels (N,H,W) int32, count (N,) int32.  The labelled set is mask != 0, with
+ * background != 0 it is mask == 0.  connectivity 4 (edge neighbours) or 8 (edge and corner neighbours).  labels is 0 outside
+ * the labelled set and 1..count[n] inside, numbered per image in raster order of each component's first pixel: the array
+ * scipy.ndimage.label(mask, structure) returns (structure None / ones((3,3))).  Components never cross from one image into the
+ * next.  Scheme: union-find in LDS per MEDT_LABEL_TILE_H x MEDT_LABEL_TILE_W tile, atomicMin across the tile edges on a parent
+ * map in the workspace, flatten, a fixed-order two-level prefix sum of the root flags, renumber; six launches, no workgroup
+ * ever waits on another, every loop ends by its own progress.  A component's provisional label is its smallest pixel index
+ * whatever order the merges land in and the ranks are integers summed in a fixed order, so the result is exact and
+ * bit-identical from run to run.  workspace: medt_label_workspace_bytes(N,H,W) bytes (the parent map and the scan partials),
+ * 16-byte aligned; a smaller workspace_bytes is MEDT_EWORKSPACE.  mask, labels and the workspace must not overlap.
+ *
+ * medt_label_tables: labels (N,H,W) int32 with values in [0, stride) -> area (N,stride) int32, area[n,l] = pixels of label l
+ * (slot 0: the unlabelled rest), frame (N,stride) uint8, frame[n,l] = 1 when component l >= 1 has a pixel in row 0, row H-1,
+ * column 0 or column W-1, else 0 (slot 0 stays 0).  The call clears both tables itself.  max_count: the largest count of the
+ * batch as the caller knows it; stride <= max_count is MEDT_EINVAL.  Labels outside [0, stride) are not counted.
+ *
+ * medt_label_select: out[n,y,x] = 255 when keep[n, labels[n,y,x]] != 0 or (mask != NULL and mask[n,y,x] != 0), else 0; keep
+ * (N,stride) uint8, out (N,H,W) uint8 (may be mask itself).  A keep table of area >= A over a foreground labelling is "drop
+ * small objects"; a keep table of frame == 0 over a 4-connected background labelling, OR-ed with the mask, is "fill holes".
+ *
+ * Integer atomics only (order-independent).  16-byte accesses when W % 4 == 0 and the pointers are aligned (int32 maps to 16
+ * bytes, uint8 maps to 4), element accesses otherwise.  1 <= H, W <= MEDT_LABEL_MAX_DIM and N*H*W below 2^31
+ * (MEDT_EUNSUPPORTED beyond, checked on the host before any launch).  Null pointers, a connectivity other than 4 or 8 and
+ * stride <= max_count are MEDT_EINVAL.  The caller owns all memory. */
+#define MEDT_LABEL_TILE_H  16
+#define MEDT_LABEL_TILE_W  64
+#define MEDT_LABEL_MAX_DIM 4096
+size_t medt_label_workspace_bytes(int N, int H, int W);      /* 0 for a geometry the calls refuse */
+int medt_label_components(const uint8_t* mask, int32_t* labels, int32_t* count, void* workspace, size_t workspace_bytes, int N,
+                          int H, int W, int connectivity, int background, void* stream);
+int medt_label_tables(const int32_t* labels, int32_t* area, uint8_t* frame, int N, int H, int W, int stride, int max_count,
+                      void* stream);
+int medt_label_select(const int32_t* labels, const uint8_t* keep, const uint8_t* mask, uint8_t* out, int N, int H, int W,
+                      int stride, void* stream);
 
 #ifdef __cplusplus
 }

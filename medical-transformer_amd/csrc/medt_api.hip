@@ -1037,4 +1037,57 @@ int medt_edt_rows(const int32_t* g2, const uint8_t* select, int32_t* d2, int N, 
     return edt_rows(g2, select, d2, N, H, W, (hipStream_t)stream);
 }
 
+static int label_geometry(const char* what, int N, int H, int W) {
+    if (N < 1 || H < 1 || W < 1) {
+        set_error("%s: bad arguments (%d images of %d x %d)", what, N, H, W); return MEDT_EINVAL;
+    }
+    if (H > MEDT_LABEL_MAX_DIM || W > MEDT_LABEL_MAX_DIM) {
+        set_error("%s: %d x %d maps: at most %d pixels per side", what, H, W, MEDT_LABEL_MAX_DIM); return MEDT_EUNSUPPORTED;
+    }
+    if ((size_t)N * H * W >= ((size_t)1 << 31)) {
+        set_error("%s: %d maps of %d x %d: 2^31 elements or more", what, N, H, W); return MEDT_EUNSUPPORTED;
+    }
+    return MEDT_OK;
+}
+
+size_t medt_label_workspace_bytes(int N, int H, int W) {
+    if (label_geometry("label_workspace_bytes", N, H, W)) return 0;
+    return label_workspace_bytes(N, H, W);
+}
+
+int medt_label_components(const uint8_t* mask, int32_t* labels, int32_t* count, void* workspace, size_t workspace_bytes, int N,
+                          int H, int W, int connectivity, int background, void* stream) {
+    if (const int rc = label_geometry("label_components", N, H, W)) return rc;
+    if (!mask || !labels || !count || !workspace) { set_error("label_components: null mask, labels, count or workspace"); return MEDT_EINVAL; }
+    if (connectivity != 4 && connectivity != 8) { set_error("label_components: connectivity %d (4 or 8)", connectivity); return MEDT_EINVAL; }
+    if ((uintptr_t)workspace % 16) { set_error("label_components: the workspace must be 16-byte aligned"); return MEDT_EINVAL; }
+    const size_t need = label_workspace_bytes(N, H, W);
+    if (workspace_bytes < need) { set_error("workspace too small: need %zu", need); return MEDT_EWORKSPACE; }
+    return label_components(mask, labels, count, workspace, N, H, W, connectivity, background, (hipStream_t)stream);
+}
+
+int medt_label_tables(const int32_t* labels, int32_t* area, uint8_t* frame, int N, int H, int W, int stride, int max_count,
+                      void* stream) {
+    if (const int rc = label_geometry("label_tables", N, H, W)) return rc;
+    if (!labels || !area || !frame) { set_error("label_tables: null labels, area or frame"); return MEDT_EINVAL; }
+    if (max_count < 0 || stride <= max_count) {
+        set_error("label_tables: stride %d cannot hold the labels 0..%d", stride, max_count); return MEDT_EINVAL;
+    }
+    return label_tables(labels, area, frame, N, H, W, stride, (hipStream_t)stream);
+}
+
+int medt_label_select(const int32_t* labels, const uint8_t* keep, const uint8_t* mask, uint8_t* out, int N, int H, int W,
+                      int stride, void* stream) {
+    if (const int rc = label_geometry("label_select", N, H, W)) return rc;
+    if (!labels || !keep || !out) { set_error("label_select: null labels, keep or out"); return MEDT_EINVAL; }
+    if (stride < 1) { set_error("label_select: stride %d", stride); return MEDT_EINVAL; }
+    return label_select(labels, keep, mask, out, N, H, W, stride, (hipStream_t)stream);
+}
+
 }  // extern "C"
+
+#ifdef MEDT_LANE_EMU
+// The lane emulator builds a fixed list of translation units (tests/test_lane_emu.py); label.hip, which the product compiles as
+// a unit of its own (medt_amd/build.py), reaches the emulated library through this one, as it stands.
+#include "label.hip"
+#endif

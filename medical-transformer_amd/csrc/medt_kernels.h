@@ -132,6 +132,13 @@ int augment_apply(const uint8_t* image, const uint8_t* mask, const float* params
 // exact squared Euclidean distance transform in two passes (medt_abi.h): columns (of the mask, or of its border), then rows
 int edt_cols(const uint8_t* mask, int32_t* g2, int N, int H, int W, int border_mode, hipStream_t s);
 int edt_rows(const int32_t* g2, const uint8_t* select, int32_t* d2, int N, int H, int W, hipStream_t s);
+// connected-component labelling, component tables, table-driven select (label.hip; medt_abi.h)
+size_t label_workspace_bytes(int N, int H, int W);
+int label_components(const uint8_t* mask, int32_t* labels, int32_t* count, void* workspace, int N, int H, int W, int connectivity,
+                     int background, hipStream_t s);
+int label_tables(const int32_t* labels, int32_t* area, uint8_t* frame, int N, int H, int W, int stride, hipStream_t s);
+int label_select(const int32_t* labels, const uint8_t* keep, const uint8_t* mask, uint8_t* out, int N, int H, int W, int stride,
+                 hipStream_t s);
 int logo_merge_fwd(const float* x, const float* yp, float* y, int N, int C, int S, int P, int G, hipStream_t s);
 int logo_merge_bwd(const float* dy, float* dx, float* dyp, int N, int C, int S, int P, int G, hipStream_t s);
 int ce_parts(size_t npix);

@@ -157,6 +157,10 @@ SIGNATURES = {
     "medt_augment_apply": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p]),
     "medt_edt_cols": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "medt_edt_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
+    "medt_label_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "medt_label_components": (C.c_int, [C.c_void_p] * 4 + [C.c_size_t] + [C.c_int] * 5 + [C.c_void_p]),
+    "medt_label_tables": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "medt_label_select": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
 }
 
 

@@ -672,3 +672,104 @@ def surface_d2(a, b, out=None):
     L.check(lib.medt_edt_cols(mb.data_ptr(), g2.data_ptr(), N, H, W, 1, _stream()), "medt_edt_cols")
     L.check(lib.medt_edt_rows(g2.data_ptr(), ma.data_ptr(), d2.data_ptr(), N, H, W, _stream()), "medt_edt_rows")
     return d2
+
+
+# --------------------------------------------------------------------------- #
+# connected-component labelling, component tables, mask clean-ups (metrics.object_scores)
+# --------------------------------------------------------------------------- #
+LABEL_TILE = (16, 64)       # (MEDT_LABEL_TILE_H, MEDT_LABEL_TILE_W) of include/medt_abi.h: the tile of the LDS union-find
+
+
+def _label_maps(what, labels, counts):
+    """int32 (N,H,W) or (H,W) label map + int32 (N,) counts on its device -> contiguous (N,H,W) view, counts."""
+    _require_device(labels.new_empty(0, dtype=torch.float32))
+    if labels.dtype != torch.int32 or labels.dim() not in (2, 3) or labels.numel() == 0:
+        raise L.MedtError(f"{what}: an int32 (N,H,W) or (H,W) label map expected")
+    lab = labels.contiguous().reshape(-1, *labels.shape[-2:])
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (lab.shape[0],) or counts.device != labels.device:
+        raise L.MedtError(f"{what}: counts must be int32 ({lab.shape[0]},) on the label map's device")
+    return lab, counts.contiguous()
+
+
+def label(mask, connectivity=8, background=False, out=None):
+    """uint8 (N,H,W) or (H,W) mask -> (labels, counts): the connected components of mask != 0 (background=True: of mask == 0)
+    at connectivity 4 or 8.  labels: int32 of the mask's shape, 0 outside the labelled set, 1..counts[n] inside, numbered per
+    image in raster order of each component's first pixel -- `scipy.ndimage.label(mask, structure)[0]` with structure None (4) or
+    np.ones((3,3)) (8), bit for bit and the same on every run.  counts: int32 (N,).  Components never join across images.
+    At most 4096 pixels per side.  out: an int32 tensor to write the labels into (a view that is not 16-byte aligned takes the
+    kernels' element accesses)."""
+    (m,) = _edt_masks("label", mask)
+    N, H, W = m.shape
+    if connectivity not in (4, 8):
+        raise L.MedtError(f"label: connectivity {connectivity!r} (4 or 8)")
+    labels = _edt_out("label", out, mask)
+    counts = torch.empty(N, device=m.device, dtype=torch.int32)
+    lib = L.lib()
+    need = lib.medt_label_workspace_bytes(N, H, W)             # (0 for a geometry the call below refuses, with the reason)
+    workspace = torch.empty(max((need + 3) // 4, 4), device=m.device, dtype=torch.int32)
+    L.check(lib.medt_label_components(m.data_ptr(), labels.data_ptr(), counts.data_ptr(), workspace.data_ptr(), need, N, H, W,
+                                      int(connectivity), int(bool(background)), _stream()), "medt_label_components")
+    return labels, counts
+
+
+def label_tables(labels, counts):
+    """Label map (N,H,W) or (H,W) int32 and its counts (N,) -> (area, frame), both (N, stride) with stride = counts.max() + 1
+    (one host sync): int32 area[n,l] = pixels of label l (slot 0: the unlabelled rest) and uint8 frame[n,l] = 1 when component
+    l has a pixel in the first or last row or column of its image."""
+    lab, cnt = _label_maps("label_tables", labels, counts)
+    N, H, W = lab.shape
+    top = int(cnt.max())
+    stride = top + 1
+    area = torch.empty(N, stride, device=lab.device, dtype=torch.int32)
+    frame = torch.empty(N, stride, device=lab.device, dtype=torch.uint8)
+    L.check(L.lib().medt_label_tables(lab.data_ptr(), area.data_ptr(), frame.data_ptr(), N, H, W, stride, top, _stream()),
+            "medt_label_tables")
+    return area, frame
+
+
+def _label_select(lab, keep, mask, shape):
+    N, H, W = lab.shape
+    out = torch.empty(N, H, W, device=lab.device, dtype=torch.uint8)
+    keep = keep.to(torch.uint8).contiguous()
+    L.check(L.lib().medt_label_select(lab.data_ptr(), keep.data_ptr(), None if mask is None else mask.data_ptr(), out.data_ptr(),
+                                      N, H, W, keep.shape[1], _stream()), "medt_label_select")
+    return out.reshape(shape)
+
+
+def remove_small_objects(mask, min_area, connectivity=8):
+    """uint8 mask (N,H,W) or (H,W) -> uint8 {0,255} mask of the same shape that keeps the connected components of mask != 0
+    with at least min_area pixels."""
+    (m,) = _edt_masks("remove_small_objects", mask)
+    labels, counts = label(m, connectivity)
+    area, _ = label_tables(labels, counts)
+    keep = area >= int(min_area)
+    keep[:, 0] = False
+    return _label_select(labels, keep, None, mask.shape)
+
+
+def fill_holes(mask):
+    """uint8 mask (N,H,W) or (H,W) -> uint8 {0,255} mask: mask != 0 with its holes filled,
+    `scipy.ndimage.binary_fill_holes(mask != 0)` -- the 4-connected components of the background that do not reach the image's
+    frame are set."""
+    (m,) = _edt_masks("fill_holes", mask)
+    labels, counts = label(m, 4, background=True)
+    _, frame = label_tables(labels, counts)
+    keep = frame == 0
+    keep[:, 0] = False
+    return _label_select(labels, keep, m, mask.shape)
+
+
+def label_overlaps(la, ca, lb, cb):
+    """Two label maps of one shape with their counts -> int64 (M,4) rows (n, a, b, |a ∩ b|) for every pair of labels a > 0 of
+    la and b > 0 of lb that share a pixel of image n, sorted by (n, a, b).  (A torch.unique over an int64 key: plumbing.)"""
+    A, ca = _label_maps("label_overlaps", la, ca)
+    B, cb = _label_maps("label_overlaps", lb, cb)
+    if A.shape != B.shape or A.device != B.device:
+        raise L.MedtError("label_overlaps: label maps of one shape on one device expected")
+    N = A.shape[0]
+    sa, sb = int(ca.max()) + 1, int(cb.max()) + 1
+    a, b = A.reshape(N, -1).long(), B.reshape(N, -1).long()
+    n = torch.arange(N, device=A.device, dtype=torch.int64).unsqueeze(1).expand_as(a)
+    both = (a > 0) & (b > 0)
+    key, cnt = torch.unique(((n * sa + a) * sb + b)[both], return_counts=True)          # (sorted)
+    return torch.stack([key // (sa * sb), key // sb % sa, key % sb, cnt], dim=1)

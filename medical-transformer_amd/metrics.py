@@ -127,3 +127,109 @@ def surface_scores(pred_mask, target_mask):
         out["hd95"][n] = float(root[lo]) + (float(root[hi]) - float(root[lo])) * (pos - lo)
         out["assd"][n] = 0.5 * (float(ab.double().sqrt().mean()) + float(ba.double().sqrt().mean()))
     return out
+
+
+def _object_scores_image(ap, ag, rows):
+    """The scores of one image from integer tables: ap / ag the pixel counts of the predicted / target objects (index 0 = object
+    1), rows the (j, i, I) triples with I = |G_i ∩ P_j| > 0, sorted by (j, i), labels from 1."""
+    kp, kg = len(ap), len(ag)
+    nan = float("nan")
+    if kp == 0 and kg == 0:
+        return (nan,) * 6
+    if kp == 0 or kg == 0:
+        return (0.0,) * 6
+    best_i = {}                        # j -> (I, i): the target object P_j overlaps most; ties to the lowest i
+    best_j = {}                        # i -> (I, j): the predicted object G_i overlaps most; ties to the lowest j
+    best_iou = {}                      # i -> (IoU, j, I)
+    tp_pq, sum_iou = 0, 0.0
+    for j, i, I in rows:               # (sorted by (j, i): a strict > keeps the lowest index on both sides)
+        if j not in best_i or I > best_i[j][0]:
+            best_i[j] = (I, i)
+        if i not in best_j or I > best_j[i][0]:
+            best_j[i] = (I, j)
+        union = ag[i - 1] + ap[j - 1] - I
+        iou = I / union
+        if i not in best_iou or iou > best_iou[i][0]:
+            best_iou[i] = (iou, j, I)
+        if 2 * I > union:              # IoU > 0.5 in integers; an object is in at most one such pair
+            tp_pq += 1
+            sum_iou += iou
+    # GlaS object F1
+    tp, hit = 0, set()
+    for j, (I, i) in best_i.items():
+        if 2 * I >= ag[i - 1]:
+            tp += 1
+            hit.add(i)
+    f1 = 2.0 * tp / (2 * tp + (kp - tp) + (kg - len(hit)))
+    # GlaS object Dice
+    tot_g, tot_p = sum(ag), sum(ap)
+    sg = sum((ag[i - 1] / tot_g) * (2.0 * I / (ag[i - 1] + ap[j - 1])) for i, (I, j) in sorted(best_j.items()))
+    sp = sum((ap[j - 1] / tot_p) * (2.0 * I / (ag[i - 1] + ap[j - 1])) for j, (I, i) in sorted(best_i.items()))
+    dice = 0.5 * (sg + sp)
+    # AJI
+    C = U = 0
+    used = set()
+    for i in range(1, kg + 1):
+        if i in best_iou:
+            _, j, I = best_iou[i]
+            C += I
+            U += ag[i - 1] + ap[j - 1] - I
+            used.add(j)
+        else:
+            U += ag[i - 1]
+    U += sum(ap[j - 1] for j in range(1, kp + 1) if j not in used)
+    aji = C / U
+    # PQ
+    dq = tp_pq / (tp_pq + (kp - tp_pq) / 2 + (kg - tp_pq) / 2)
+    sq = sum_iou / tp_pq if tp_pq else 0.0
+    return f1, dice, aji, dq * sq, dq, sq
+
+
+def object_scores(pred, target, connectivity=8, labelled=False):
+    """Per-image object-level scores of a prediction against a target, on the device.  pred / target: uint8 masks (N,H,W) or
+    (H,W), foreground = mask != 0, labelled here at `connectivity` (4 or 8; 8 is MATLAB's bwlabel); or with labelled=True int32
+    label maps with consecutive labels 1..K per image, taken as given (instance annotations).
+
+    With P_j the predicted objects, G_i the target objects, I[i,j] = |G_i ∩ P_j|, ties to the lowest index:
+      f1    GlaS object F1: P_j is a true positive when the G_i* it overlaps most has 2 I[i*,j] >= |G_i*|; FP = Kp - TP,
+            FN = Kg - the distinct i* among the true positives; 2TP / (2TP + FP + FN)
+      dice  GlaS object Dice: 0.5 (sum_i |G_i|/sum|G| D(G_i, P_j*(i)) + sum_j |P_j|/sum|P| D(G_i*(j), P_j)), D = 2|A∩B| / (|A|+|B|),
+            0 without a partner
+      aji   Aggregated Jaccard Index: every G_i in order takes the P_j of largest IoU among those it touches, C += I,
+            U += |G_i ∪ P_j| (else U += |G_i|); then U += |P_j| of every P_j never taken; C / U
+      pq    panoptic quality: matches are the pairs with IoU > 0.5; dq = TP / (TP + FP/2 + FN/2), sq = mean IoU of the matches
+            (0 without one), pq = dq sq
+    -> {"f1", "dice", "aji", "pq", "dq", "sq": float64 (N,), "n_pred", "n_gt": int64 (N,), "valid": bool (N,)} on the CPU.
+    valid is False and the scores NaN only where BOTH images have no object; with exactly one side empty every score is 0.
+
+    These follow the published descriptions of the GlaS and MoNuSeg challenges and of PQ; the challenges' own MATLAB / Python
+    evaluation code was not available, so no bit-compatibility with it is claimed.
+
+    Labelling, the area tables and the overlap table run on the device (medt_amd.ops.label / label_tables / label_overlaps);
+    only those integer tables come to the host, where the scores are computed in float64 per image."""
+    from medt_amd import ops
+    if labelled:
+        lp, lg = pred, target
+        N = lp.reshape(-1, *lp.shape[-2:]).shape[0]
+        cp = lp.reshape(N, -1).amax(dim=1).to(torch.int32)
+        cg = lg.reshape(N, -1).amax(dim=1).to(torch.int32)
+    else:
+        lp, cp = ops.label(pred, connectivity)
+        lg, cg = ops.label(target, connectivity)
+    area_p, _ = ops.label_tables(lp, cp)
+    area_g, _ = ops.label_tables(lg, cg)
+    rows = ops.label_overlaps(lp, cp, lg, cg).cpu().tolist()
+    area_p, area_g, cp, cg = area_p.cpu().tolist(), area_g.cpu().tolist(), cp.cpu().tolist(), cg.cpu().tolist()
+    N = len(cp)
+    per_image = [[] for _ in range(N)]
+    for n, j, i, I in rows:
+        per_image[n].append((j, i, I))
+    keys = ("f1", "dice", "aji", "pq", "dq", "sq")
+    out = {k: torch.empty(N, dtype=torch.float64) for k in keys}
+    out["n_pred"], out["n_gt"] = torch.tensor(cp, dtype=torch.int64), torch.tensor(cg, dtype=torch.int64)
+    out["valid"] = (out["n_pred"] > 0) | (out["n_gt"] > 0)
+    for n in range(N):
+        got = _object_scores_image(area_p[n][1:cp[n] + 1], area_g[n][1:cg[n] + 1], per_image[n])
+        for k, v in zip(keys, got):
+            out[k][n] = v
+    return out

@@ -3,7 +3,8 @@
 train.py (with or without DataParallel's "module." prefix), runs the network in eval mode and writes the
 thresholded channel-1 prediction of every validation image as <direc>/<filename>.  The reference reads an
 undefined args.aug (test.py:62) and dies; here the flag exists and is ignored.  --surface on adds the surface-distance scores
-(HD, HD95, ASSD) of the written masks behind the F1 / mIoU / PA line."""
+(HD, HD95, ASSD) of the written masks behind the F1 / mIoU / PA line, --objects on the object-level scores (object F1 and Dice,
+AJI, PQ) behind those; --fill_holes on and --min_object AREA clean the masks on the device before they are written and scored."""
 import argparse
 import os
 
@@ -50,6 +51,19 @@ parser.add_argument('--surface', default='off', choices=['off', 'on'],
                          'against the label maps -- Hausdorff distance, its 95th percentile and the average symmetric surface '
                          'distance, in pixels, means over the images whose mask and label map both have foreground '
                          '(metrics.surface_scores: distance transforms on the device)')
+parser.add_argument('--objects', default='off', choices=['off', 'on'],
+                    help='(not in the reference) on: a further score line with the object-level scores of the written masks against '
+                         'the label maps -- GlaS object F1 and object Dice, Aggregated Jaccard Index, panoptic quality -- means over '
+                         'the images in which the mask or the label map has an object (metrics.object_scores: connected-component '
+                         'labelling on the device)')
+parser.add_argument('--connectivity', type=int, default=8, choices=[4, 8],
+                    help="(not in the reference) connectivity of the objects of --objects and --min_object (8: MATLAB's bwlabel)")
+parser.add_argument('--min_object', type=int, default=0, metavar='AREA',
+                    help='(not in the reference) > 0: objects of fewer than AREA pixels are removed from every mask before it is '
+                         'written and scored (medt_amd.ops.remove_small_objects)')
+parser.add_argument('--fill_holes', default='off', choices=['off', 'on'],
+                    help='(not in the reference) on: the holes of every mask are filled before small objects are removed and the '
+                         'mask is written and scored (medt_amd.ops.fill_holes = scipy.ndimage.binary_fill_holes)')
 
 
 def main():
@@ -78,6 +92,28 @@ def main():
     os.makedirs(fulldir, exist_ok=True)
     scores = []
     surface = [] if args.surface == "on" else None     # per-batch metrics.surface_scores of (mask, target > 0), eager, behind the replay
+    objects = [] if args.objects == "on" else None     # per-batch metrics.object_scores of the same pairs
+    cleaning = args.fill_holes == "on" or args.min_object > 0
+
+    def clean(mask, target, like):
+        """The clean-ups of a uint8 {0,255} mask batch on the device, holes first, and the {tp, fp, fn, tn} counts of the result
+        against target > 0 in the layout and dtype of the replayed counts: every score line describes the files written."""
+        from medt_amd import ops
+        if args.fill_holes == "on":
+            mask = ops.fill_holes(mask)
+        if args.min_object > 0:
+            mask = ops.remove_small_objects(mask, args.min_object, args.connectivity)
+        p, t = (mask != 0).reshape(mask.shape[0], -1), (target > 0).reshape(mask.shape[0], -1)
+        counts = torch.stack([(p & t).sum(1), (p & ~t).sum(1), (~p & t).sum(1), (~p & ~t).sum(1)], dim=1).to(like.dtype)
+        return mask, counts
+
+    def score(mask, target):
+        t = (target > 0).to(torch.uint8)
+        if surface is not None:
+            surface.append(metrics.surface_scores(mask, t))
+        if objects is not None:
+            objects.append(metrics.object_scores(mask, t, args.connectivity))
+
     # forward + the device-side counts as ONE replayed hipGraph per image shape (medt_amd.trainer.InferStep): an eager
     # forward is ~110 dependent launches issued from Python and is host-bound
     infer = InferStep(model)
@@ -89,10 +125,17 @@ def main():
         xs = torch.cat([it[0] for it in items] + [items[-1][0]] * (gather - len(items))).to(device)
         ys = torch.cat([it[1].long().reshape(1, *it[0].shape[2:]) for it in items] + [items[-1][1].long().reshape(1, *items[-1][0].shape[2:])] * (gather - len(items))).to(device)
         y_out, counts = infer(xs, ys)
+        if cleaning:
+            mask, cleaned = clean((y_out[:len(items), 1] >= 0.5).to(torch.uint8) * 255, ys[:len(items)], counts)
+            scores.append(cleaned)
+            score(mask, ys[:len(items)])
+            mask = mask.cpu().numpy()
+            for k, it in enumerate(items):
+                imwrite(fulldir + it[2], mask[k])
+            return
         scores.append(counts[:len(items)].clone())
-        if surface is not None:                        # the mask the PNG holds (same comparison, on the device) against target > 0
-            surface.append(metrics.surface_scores((y_out[:len(items), 1] >= 0.5).to(torch.uint8) * 255,
-                                                  (ys[:len(items)] > 0).to(torch.uint8)))
+        if surface is not None or objects is not None:   # the mask the PNG holds (same comparison, on the device) against target > 0
+            score((y_out[:len(items), 1] >= 0.5).to(torch.uint8) * 255, ys[:len(items)])
         yHaT = (y_out[:len(items)].detach().cpu().numpy() >= 0.5).astype(np.uint8) * 255
         for k, it in enumerate(items):
             imwrite(fulldir + it[2], yHaT[k, 1, :, :])
@@ -108,9 +151,12 @@ def main():
             image_filename = rest[0][0] if isinstance(rest[0][0], str) else '%s.png' % str(batch_idx + 1).zfill(3)
             target = y_batch.long().reshape(1, *X_batch.shape[2:]).to(device)
             _, mask, counts = winfer(X_batch.to(device), target)
+            if cleaning:
+                mask, counts = clean(mask.unsqueeze(0), target, counts)
+                mask = mask[0]
             scores.append(counts)
-            if surface is not None:
-                surface.append(metrics.surface_scores(mask.unsqueeze(0), (target > 0).to(torch.uint8)))
+            if surface is not None or objects is not None:
+                score(mask.unsqueeze(0), target)
             imwrite(fulldir + image_filename, mask.cpu().numpy())
         valloader = ()
     for batch_idx, (X_batch, y_batch, *rest) in enumerate(valloader):
@@ -133,6 +179,11 @@ def main():
         hd, hd95, assd = (torch.cat([s[k] for s in surface])[valid] for k in ("hd", "hd95", "assd"))
         print("surface images {}/{}  HD {:.4f}  HD95 {:.4f}  ASSD {:.4f}".format(
             int(valid.sum()), len(valid), *(v.mean().item() if len(v) else float("nan") for v in (hd, hd95, assd))))
+    if objects:
+        valid = torch.cat([s["valid"] for s in objects])
+        f1o, diceo, aji, pq = (torch.cat([s[k] for s in objects])[valid] for k in ("f1", "dice", "aji", "pq"))
+        print("objects images {}/{}  F1obj {:.4f}  Diceobj {:.4f}  AJI {:.4f}  PQ {:.4f}".format(
+            int(valid.sum()), len(valid), *(v.mean().item() if len(v) else float("nan") for v in (f1o, diceo, aji, pq))))
 
 
 if __name__ == "__main__":
