@@ -74,3 +74,38 @@ def rel_err(a, b):
 
 def param_names(model_name, S, chan=3):
     return [k for k, _ in manifest()[f"{model_name}/{S}/{chan}"]["params"]]
+
+
+GATE_SUFFIXES = (".f_qr", ".f_kr", ".f_sve", ".f_sv")
+
+
+def oracle_trajectory(name, st, x, y, dtype, schedule, train_keys, gate_keys=(), gates_join=None, ulp_seed=None):
+    """The reference's loop (train.py:140,156-161: forward, LogNLLLoss, backward, Adam with lr 1e-3 / weight_decay 1e-5) on the
+    CPU oracle, from the state `st`.  Step i runs on the first schedule[i] images of (x, y).  Parameters in `train_keys` that
+    receive a gradient are updated from the first step on; those in `gate_keys` stay frozen before step `gates_join`
+    (0-based) and train from it on.  Every parameter counts its own Adam step from 1 at its first update, as
+    torch.optim.Adam does.  ulp_seed: the initial trained weights and the input moved by one float32 ulp in random directions
+    first.  -> (loss of every step, final state)."""
+    ost, xin = O.clone_state(st, dtype), x.to(dtype)
+    train_keys, gate_keys = set(train_keys), set(gate_keys)
+    if ulp_seed is not None:
+        g = torch.Generator().manual_seed(ulp_seed)
+        nudge = lambda t: torch.nextafter(t, torch.where(torch.rand(t.shape, generator=g) < 0.5, -1.0, 1.0) * float("inf"))
+        ost = {k: (nudge(v) if (v.is_floating_point() and k in train_keys) else v) for k, v in ost.items()}
+        xin = nudge(xin)
+    mom, count, out_losses = {}, {}, []
+    for i, n in enumerate(schedule):
+        live = train_keys | gate_keys if (gates_join is not None and i >= gates_join) else train_keys
+        leaf = {k: (v.clone().requires_grad_(True) if k in live else v) for k, v in ost.items()}
+        loss = O.log_nll_loss(O.forward(name, xin[:n], leaf, True), y[:n])
+        loss.backward()
+        out_losses.append(loss.item())
+        for k in ost:
+            if k in live and leaf[k].grad is not None:
+                m, v = mom.get(k, (torch.zeros_like(ost[k]), torch.zeros_like(ost[k])))
+                count[k] = count.get(k, 0) + 1
+                pnew, m, v = O.adam_step(ost[k], leaf[k].grad, m, v, count[k])
+                ost[k], mom[k] = pnew.detach(), (m, v)
+            else:
+                ost[k] = leaf[k].detach()                    # buffers (running statistics) as updated by the forward
+    return out_losses, ost

@@ -1,0 +1,242 @@
+"""Whole networks away from the corner the other GPU tests sit on (three input channels, batches of 1, 2, 4 or 8): one input
+channel (train.py / test.py --gray yes build the model with imgchan=1, and conv_stem7_ok wants Cin == 3, so a gray stem takes the
+generic convolution kernels) and the batch sizes a ragged last batch or an odd --batch_size gives (3, 5, 7; 1 in training mode).
+Every reference is the live fp64 oracle (oracle.medt_oracle) or plain slicing; the oracle itself is pinned against the reference at
+one channel by tests/test_oracle_vs_reference.py."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import helpers as H
+from oracle import medt_oracle as O
+from test_model_gpu import build
+
+pytestmark = pytest.mark.gpu
+PKG = os.path.join(H.ROOT, "medical-transformer_amd")
+
+
+def _as_device(t, device):
+    """On the emulated device (pytest --emulate) CPU tensors stand in for device tensors."""
+    if device.type == "cpu":
+        from emu_device import DeviceTensor
+        return t.as_subclass(DeviceTensor)
+    return t.to(device)
+
+
+def _evalgrad_vs_oracle(name, S, N, chan, seed, device):
+    """Running-statistics mode after test_model_gpu.py::test_gated_evalgrad_vs_oracle_full: logits to 1e-4, every gradient tensor
+    in full to 1e-3 of max(|g|max, 1e-3 gmax); a parameter without an oracle gradient has none, or all zeros."""
+    model = build(name, S, device, chan)
+    st = O.randomize_state({k: v.cpu() for k, v in model.state_dict().items()}, seed)
+    model.load_state_dict(st)
+    for p in model.parameters():
+        p.requires_grad_(True)
+    model.eval()
+    x, y = H.seeded_input(seed + 1, N, chan, S)
+    out = model(x.to(device))
+    torch.nn.functional.cross_entropy(out, y.to(device)).backward()
+    ost = O.clone_state(st, torch.float64, requires_grad=True)
+    oout = O.forward(name, x.double(), ost, False)
+    O.log_nll_loss(oout, y).backward()
+    err = H.rel_err(out, oout)
+    gmax = max(v.grad.abs().max().item() for v in ost.values() if v.grad is not None)
+    worst, checked = (0.0, None), 0
+    for k, p in model.named_parameters():
+        g = ost[k].grad
+        if g is None:
+            assert p.grad is None or p.grad.abs().max().item() == 0, k
+            continue
+        assert p.grad is not None, k
+        scale = max(g.abs().max().item(), 1e-3 * gmax)
+        e = (p.grad.double().cpu() - g).abs().max().item() / scale
+        worst = max(worst, (e, k))
+        checked += 1
+    print(f"{name} {S} px N={N} chan={chan} running statistics: logits rel err {err:.2e} (bound 1e-4); worst gradient rel err "
+          f"{worst[0]:.2e} on {worst[1]} over {checked} tensors (bound 1e-3)")
+    assert err < 1e-4, err
+    assert worst[0] < 1e-3, worst
+    assert checked > 100
+
+
+# ---- A. one input channel ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,S,N", [("axialunet", 64, 2), ("gatedaxialunet", 64, 3), ("MedT", 128, 1), ("logo", 128, 1)])
+def test_gray_evalgrad_vs_oracle_full(name, S, N, device):
+    """imgchan=1, running-statistics mode: logits and every gradient tensor in full against the live fp64 oracle."""
+    _evalgrad_vs_oracle(name, S, N, 1, 121, device)
+
+
+def test_gray_patch_gather_and_merge(device):
+    """patch_gather on a one-channel 128-px image and logo_merge on one-channel maps, bit-exact against slicing (the 16 patches
+    cover a 128-px map: the merge is one exactly rounded fp32 addition per element, its gradients are copies)."""
+    from medt_amd import ops
+    torch.manual_seed(128)
+    N, S = 3, 128
+    img = torch.randn(N, 1, S, S)
+    xp = ops.patch_gather(img.to(device))
+    want = torch.cat([img[:, :, 32 * i:32 * i + 32, 32 * j:32 * j + 32] for i in range(4) for j in range(4)], 0)
+    assert xp.shape == (16 * N, 1, 32, 32) and torch.equal(xp.cpu(), want)
+    x, yp, dout = torch.randn(N, 1, S, S), torch.randn(16 * N, 1, 32, 32), torch.randn(N, 1, S, S)
+    xr, pr = x.clone().requires_grad_(True), yp.clone().requires_grad_(True)
+    loc = xr.clone()
+    for p in range(16):
+        i, j = divmod(p, 4)
+        loc[:, :, 32 * i:32 * i + 32, 32 * j:32 * j + 32] = pr[p * N:(p + 1) * N]
+    yr = xr + loc
+    (yr * dout).sum().backward()
+    xd, pd = x.to(device).requires_grad_(True), yp.to(device).requires_grad_(True)
+    y = ops.logo_merge(xd, pd)
+    (y * dout.to(device)).sum().backward()
+    assert torch.equal(y.detach().cpu(), yr.detach())
+    assert torch.equal(xd.grad.cpu(), xr.grad)
+    assert torch.equal(pd.grad.cpu(), pr.grad)
+
+
+@pytest.mark.parametrize("name,S,N", [("MedT", 128, 1), ("gatedaxialunet", 64, 3)])
+def test_gray_replayed_eval_forward_equals_eager(name, S, N, device):
+    """InferStep with one input channel: the replay is the eager no-grad forward, bit for bit (call 0 captures, calls 1-2 replay
+    with fresh inputs).  (The emulated device has no graphs: InferStep's eager route there.)"""
+    from medt_amd.trainer import InferStep
+    model = build(name, S, device, 1)
+    model.load_state_dict(H.seeded_state(name, S, 3, 1))
+    model.eval()
+    infer = InferStep(model, use_graph=device.type == "cuda")
+    for k in range(3):
+        x, _ = H.seeded_input(140 + k, N, 1, S)
+        x = _as_device(x, device)
+        with torch.no_grad():
+            want = model(x)
+        got = infer(x)
+        assert got.shape == (N, 2, S, S)
+        assert torch.equal(got, want), (k, H.rel_err(got, want))
+    if device.type == "cuda":
+        assert len(infer._graphs) == 1
+
+
+def test_gray_train_then_test_cli_roundtrip(tmp_path, device):
+    """train.py --gray yes on 10 synthetic one-channel images in batches of 4, 4 and a ragged 2 for 12 epochs -- the gates join
+    after epoch 10, under graphs -- then test.py --gray yes on the last checkpoint with --gather 3 and --gather 1: return codes,
+    finite losses, the number of files written, and the two sets of maps equal up to 4 pixels whose logit sits within rounding
+    of the 0.5 threshold (test_cli_and_data.py::test_train_then_test_cli_roundtrip's bound)."""
+    if device.type != "cuda":
+        pytest.skip("the command line runs on the GPU")
+    from PIL import Image
+    env = dict(os.environ, PYTHONPATH=PKG)
+    d, out = str(tmp_path / "data"), str(tmp_path / "run")
+    r = subprocess.run([sys.executable, os.path.join(PKG, "train.py"), "--train_dataset", d, "--val_dataset", d, "--direc", out,
+                        "--gray", "yes", "--synthetic", "10", "--batch_size", "4", "--epoch", "12", "--imgsize", "32",
+                        "--modelname", "gatedaxialunet", "--save_freq", "1"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    losses = [float(v) for v in re.findall(r"epoch \[\d+/12\], loss:(\S+)", r.stdout)]
+    print("gray CLI round trip, epoch losses:", losses)
+    assert len(losses) == 12 and all(np.isfinite(losses)), r.stdout[-2000:]
+    for epoch in range(12):
+        assert len(os.listdir(os.path.join(out, str(epoch)))) == 10 + 1, epoch
+    ckpt = os.path.join(out, "11", "gatedaxialunet.pth")
+    assert os.path.exists(ckpt) and os.path.exists(out + "final_model.pth")
+    assert torch.load(ckpt, map_location="cpu")["conv1.weight"].shape[1] == 1
+    outs = {}
+    for gth in ("3", "1"):
+        rg = str(tmp_path / ("res" + gth))
+        r = subprocess.run([sys.executable, os.path.join(PKG, "test.py"), "--loaddirec", ckpt, "--val_dataset", d, "--direc", rg,
+                            "--batch_size", "1", "--modelname", "gatedaxialunet", "--imgsize", "32", "--gray", "yes",
+                            "--gather", gth], env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert "images 10 " in r.stdout, r.stdout[-500:]
+        outs[gth] = {f: np.asarray(Image.open(os.path.join(rg, f))) for f in sorted(os.listdir(rg))}
+        assert len(outs[gth]) == 10
+    diff = sum(int((outs["3"][f] != outs["1"][f]).sum()) for f in outs["1"])
+    assert diff <= 4, diff
+
+
+# ---- B. batch sizes that are not 1, 2, 4 or 8 ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,S,N", [("gatedaxialunet", 64, 3), ("gatedaxialunet", 64, 5), ("MedT", 128, 3), ("axialunet", 64, 7)])
+def test_odd_batch_evalgrad_vs_oracle_full(name, S, N, device):
+    """Three channels, running-statistics mode, N = 3, 5, 7: logits and every gradient tensor in full against the fp64 oracle."""
+    _evalgrad_vs_oracle(name, S, N, 3, 131, device)
+
+
+def _nudged(t, g):
+    """One float32 ulp up or down, at random."""
+    return torch.nextafter(t, torch.where(torch.rand(t.shape, generator=g) < 0.5, -1.0, 1.0) * float("inf"))
+
+
+@pytest.mark.parametrize("name,S,N", [("gatedaxialunet", 64, 1), ("gatedaxialunet", 64, 3), ("gatedaxialunet", 64, 5),
+                                      ("MedT", 128, 1), ("MedT", 128, 3)])
+def test_odd_batch_train_forward_and_bookkeeping(name, S, N, device):
+    """Training mode (batch statistics) at N = 1, 3, 5 from a randomize_state start: forward and bookkeeping against the fp64 oracle.
+
+    Logits: max(1e-3, 1.5 d), the form test_model_vs_reference_fixture uses, where d is the largest deviation from the fp64
+    oracle among three float32 runs OF THE ORACLE (as is; twice from parameters and input moved by one ulp, as in
+    helpers.oracle_trajectory) -- measured against the oracle, never against the product; both figures are printed.  Loss to 1e-3.
+    Every running_mean / running_var to rel_err < 1e-3 against the fp64 oracle's buffers; a buffer on which the float32 oracle
+    runs themselves miss 1e-3 is held to 4 x their deviation instead and printed.  gatedaxialunet 64: none.  MedT 128, the deep
+    local-branch layers, whose populations are 4 or 16 values per image (2 x 2 and 4 x 4 maps of one 32-px patch) -- N = 3: the
+    running_mean of layer4_p.0.{hight,width}_block.{bn_similarity,bn_output} (oracle deviation 1.0e-3 - 1.7e-3); N = 1: those four
+    (3.1e-3 - 2.2e-2) and layer4_p.0.{hight,width}_block.{bn_similarity,bn_output}.running_var, layer4_p.0.width_block.bn_qkv.running_var,
+    layer4_p.0.bn1.running_var, layer4_p.0.bn2.running_{mean,var}, layer4_p.0.downsample.1.running_var,
+    layer3_p.3.{hight,width}_block.{bn_similarity,bn_output}.running_mean, layer3_p.3.bn2.running_var and
+    layer3_p.2.width_block.bn_similarity.running_mean (1.1e-3 - 6.9e-3).  Measured on the MI355X: logits error / float32 oracle
+    deviation 3.0e-4 / 3.1e-4, 3.1e-4 / 3.1e-4, 5.5e-4 / 6.1e-4 (gatedaxialunet N = 1, 3, 5) and 4.3e-3 / 4.4e-3, 1.0e-3 / 1.2e-3
+    (MedT N = 1, 3); worst running statistic 1.2e-4 (gatedaxialunet), 8.0e-3 on a buffer the oracle's float32 runs move by 2.2e-2
+    (MedT N = 1), 1.2e-3 against 1.3e-3 (MedT N = 3).
+    Every num_batches_tracked exact (16 per step in MedT's local branch).  Every gradient finite.
+    No gradient parity here: at this state the whole-network training-mode backward is ill-conditioned in fp32 for the oracle
+    itself (its float32 runs differ from its fp64 by 0.1 - 0.6 relative; DESIGN.md 'parity floor'); the backward wiring at these
+    batch sizes is held in running-statistics mode by test_odd_batch_evalgrad_vs_oracle_full."""
+    model = build(name, S, device)
+    st = O.randomize_state({k: v.cpu() for k, v in model.state_dict().items()}, 151)
+    model.load_state_dict(st)
+    model.train()
+    x, y = H.seeded_input(152, N, 3, S)
+    out = model(x.to(device))
+    loss = torch.nn.functional.cross_entropy(out, y.to(device))
+    loss.backward()
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    params = {k for k, _ in model.named_parameters()}
+    with torch.no_grad():
+        o64 = O.clone_state(st, torch.float64)
+        want = O.forward(name, x.double(), o64, True)
+        want_loss = O.log_nll_loss(want, y).item()
+        d, bufdev = 0.0, {}
+        for sd_ in (None, 1511, 1512):
+            o32, xin = O.clone_state(st, torch.float32), x.clone()
+            if sd_ is not None:
+                g = torch.Generator().manual_seed(sd_)
+                o32 = {k: (_nudged(v, g) if (v.is_floating_point() and k in params) else v) for k, v in o32.items()}
+                xin = _nudged(xin, g)
+            d = max(d, H.rel_err(O.forward(name, xin, o32, True), want))
+            for k, v in o32.items():
+                if "running" in k:
+                    bufdev[k] = max(bufdev.get(k, 0.0), H.rel_err(v, o64[k]))
+    err, bound = H.rel_err(out, want), max(1e-3, 1.5 * d)
+    print(f"{name} {S} px N={N} train: logits rel err {err:.2e}; the float32 oracle's own deviation {d:.2e} (bound {bound:.2e}); "
+          f"loss {loss.item():.6f} vs {want_loss:.6f}")
+    assert err < bound, (err, bound)
+    assert abs(loss.item() - want_loss) < 1e-3
+    sd = model.state_dict()
+    worst, loose, nstat = (0.0, None), [], 0
+    for k, v in o64.items():
+        if k.endswith("num_batches_tracked"):
+            assert int(sd[k].item()) == int(v.item()), k
+        elif "running" in k:
+            tol = 1e-3 if bufdev[k] < 1e-3 else 4 * bufdev[k]
+            if tol > 1e-3:
+                loose.append((k, bufdev[k]))
+            e = H.rel_err(sd[k], v)
+            worst = max(worst, (e, k))
+            assert e < tol, (k, e, tol)
+            nstat += 1
+    print(f"  worst running statistic rel err {worst[0]:.2e} on {worst[1]} over {nstat} buffers; "
+          f"buffers the float32 oracle misses 1e-3 on: {loose}")
+    assert nstat > 100
+    assert int(sd["bn1.num_batches_tracked"].item()) == 1
+    if name == "MedT":
+        assert int(sd["layer1_p.0.bn1.num_batches_tracked"].item()) == int(sd["layer4_p.0.bn2.num_batches_tracked"].item()) == 16
+    for k, p in model.named_parameters():
+        assert p.grad is None or torch.isfinite(p.grad).all(), k

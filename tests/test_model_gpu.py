@@ -320,28 +320,9 @@ def test_training_trajectory_vs_oracle(device):
     train_keys = [k for k, p in model.named_parameters() if p.requires_grad]
 
     def oracle_run(dtype, ulp_seed=None):
-        """The same loop on the CPU oracle; parameters that receive a gradient are updated, the frozen gates are not.
-        ulp_seed: the initial weights and the input moved by one float32 ulp in random directions first."""
-        ost, xin = O.clone_state(st, dtype), x.to(dtype)
-        if ulp_seed is not None:
-            g = torch.Generator().manual_seed(ulp_seed)
-            nudge = lambda t: torch.nextafter(t, torch.where(torch.rand(t.shape, generator=g) < 0.5, -1.0, 1.0) * float("inf"))
-            ost = {k: (nudge(v) if (v.is_floating_point() and k in train_keys) else v) for k, v in ost.items()}
-            xin = nudge(xin)
-        mom, out_losses = {}, []
-        for t in range(1, STEPS + 1):
-            leaf = {k: (v.clone().requires_grad_(True) if k in train_keys else v) for k, v in ost.items()}
-            loss = O.log_nll_loss(O.forward(name, xin, leaf, True), y)
-            loss.backward()
-            out_losses.append(loss.item())
-            for k in ost:
-                if k in train_keys and leaf[k].grad is not None:
-                    m, v = mom.get(k, (torch.zeros_like(ost[k]), torch.zeros_like(ost[k])))
-                    pnew, m, v = O.adam_step(ost[k], leaf[k].grad, m, v, t)
-                    ost[k], mom[k] = pnew.detach(), (m, v)
-                else:
-                    ost[k] = leaf[k].detach()                    # buffers (running statistics) as updated by the forward
-        return out_losses, ost
+        """The same loop on the CPU oracle (helpers.oracle_trajectory); parameters that receive a gradient are updated, the
+        frozen gates are not.  ulp_seed: the initial weights and the input moved by one float32 ulp in random directions first."""
+        return H.oracle_trajectory(name, st, x, y, dtype, [N] * STEPS, train_keys, ulp_seed=ulp_seed)
 
     want, ost = oracle_run(torch.float64)
     # Adam turns the rounding noise of every near-zero gradient into a +-lr step, so from the second step on the loss of

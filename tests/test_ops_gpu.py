@@ -101,6 +101,11 @@ CONV_CASES = [
     (64, 48, 3, 1, 1, False, True, False, True, 8, 32, 1),      # the same tile count with BatchNorm (statistics from the split-K epilogue)
     (256, 256, 3, 2, 1, True, False, False, False, 64, 2, 1),   # decoder1_p at BASELINE size: stride 2 on 2 x 2 maps (staged wave-split backward-data, 4 of 9 taps live)
     (256, 256, 3, 2, 1, True, False, False, False, 8, 4, 1),    # decoder1 of the unets at bs 8: 4 x 4 -> 2 x 2 (every tap live somewhere)
+    # one input channel (--gray yes): conv_stem7_ok wants Cin == 3, so a gray stem takes the generic forward, backward-data and
+    # weight-gradient kernels at Ktot = 49
+    (1, 8, 7, 2, 3, False, True, False, True, 2, 32, 1),        # gray stem conv1
+    (1, 64, 7, 2, 3, False, True, False, True, 4, 32, 4),       # gray conv1_p: grouped BatchNorm, the generic kernels in place of the stem kernel
+    (1, 40, 7, 2, 3, True, False, False, True, 3, 18, 1),       # bias, odd 9 x 9 map, ragged tiles
 ]
 
 

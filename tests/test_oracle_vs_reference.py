@@ -23,17 +23,23 @@ def digest(t):
     return [list(t.shape), str(t.dtype).replace("torch.", ""), hashlib.sha256(t.numpy().tobytes()).hexdigest()]
 
 
+MODEL_CASES = [("gatedaxialunet", 64, 2, 3), ("axialunet", 64, 1, 3), ("MedT", 128, 1, 3), ("logo", 128, 1, 3),
+               # one input channel (--gray yes): the oracle tests/test_configs_gpu.py relies on
+               ("gatedaxialunet", 64, 3, 1), ("axialunet", 64, 1, 1), ("MedT", 128, 3, 1), ("logo", 128, 1, 1)]
+
+
 @pytest.mark.skipif(not ref_loader.available(), reason="reference checkout not present")
-@pytest.mark.parametrize("name,S,N", [("gatedaxialunet", 64, 2), ("axialunet", 64, 1), ("MedT", 128, 1), ("logo", 128, 1)])
-def test_model_forward_backward_fp64(name, S, N):
+@pytest.mark.parametrize("name,S,N,chan", MODEL_CASES,       # (the three-channel cases keep the ids they had before `chan` was a parameter)
+                         ids=[f"{n}-{s}-{b}" + ("" if c == 3 else f"-chan{c}") for n, s, b, c in MODEL_CASES])
+def test_model_forward_backward_fp64(name, S, N, chan):
     torch.manual_seed(0)
-    ref = ref_loader.factory(name)(img_size=S, imgchan=3)
+    ref = ref_loader.factory(name)(img_size=S, imgchan=chan)
     sd = O.randomize_state(ref.state_dict(), 3)
     ref.load_state_dict(sd)
     ref = ref.double()
     for p in ref.parameters():
         p.requires_grad_(True)
-    x, y = H.seeded_input(4, N, 3, S)
+    x, y = H.seeded_input(4, N, chan, S)
     for training in (True, False):
         ref.train(training)
         st = O.clone_state(ref.state_dict(), torch.float64, requires_grad=True)
