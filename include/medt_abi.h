@@ -39,7 +39,7 @@ extern "C" {
  * entry points were added under the same number: additions only, nothing that version 11 declared was removed or changed,
  * so a caller built against the earlier header keeps working.  The medt_label_* entry points were added under the same
  * number: additions only, nothing that version 11 declared was removed or changed, so a caller built against the earlier
- * header keeps working. */
+ * header keeps working.  medt_label_boxes and medt_pair_hausdorff were added under the same number, in the same way. */
 #define MEDT_ABI_VERSION 11
 
 #define MEDT_OK            0
@@ -495,6 +495,41 @@ int medt_label_tables(const int32_t* labels, int32_t* area, uint8_t* frame, int 
                       void* stream);
 int medt_label_select(const int32_t* labels, const uint8_t* keep, const uint8_t* mask, uint8_t* out, int N, int H, int W,
                       int stride, void* stream);
+
+/* Bounding boxes of the components and directed squared Hausdorff distances of pairs of them -- the building blocks of the
+ * object-level Hausdorff distance of GlaS (metrics.object_hausdorff), added under version 11 as the calls above were.
+ *
+ * medt_label_boxes: labels (N,H,W) int32 with values in [0, stride) -> box (N,stride,4) int32, box[n,l] = (y0, x0, y1, x1),
+ * inclusive, of label l >= 1; a label without a pixel holds (H, W, -1, -1), and so does slot 0, which only the call's own
+ * initialisation writes.  Integer atomicMin / atomicMax, reduced per workgroup in LDS first: independent of any order.
+ * Arguments, checks and limits as medt_label_tables; N*stride*4 must stay below 2^31 (MEDT_EUNSUPPORTED).
+ *
+ * medt_pair_hausdorff: la, lb (N,H,W) int32 label maps; jobs: a DEVICE table of n_jobs records of MEDT_PAIR_JOB_INTS int32,
+ * one per (pair, direction):
+ *    0 n          image                     1 query label           2 feature label
+ *    3 swap       0: the query object is in la and the feature object in lb; 1: the other way round
+ *    4..7         y0, y1, x0, x1 of the query object's bounding box (inclusive)
+ *    8, 9         x0, x1 of the feature object's bounding box
+ *   10, 11        first and last row the column pass sweeps: the union of the two objects' row ranges
+ *   12 offset     of the job's g2 in scratch, in elements; the job owns (query rows) x (feature columns) of them
+ *   13 slot       index into out that receives the job's result
+ *   14, 15        blocks the jobs in front of this one take in the column launch (ceil(feature columns / 256) each) and in
+ *                 the row launch (query rows each): non-decreasing prefix sums that start at 0; col_blocks / row_blocks are
+ *                 their totals over all n_jobs jobs
+ * out[slot] = max(out[slot], max over the pixels of the query object of the squared Euclidean distance to the nearest pixel
+ * of the feature object), an exact int32; a feature label without a pixel inside its box gives MEDT_EDT_NONE.  clear_out != 0
+ * zeroes the n_out int32 of out first (the first chunk of a job list that is issued in several calls so that the scratch
+ * stays bounded).  Two launches: the column pass of the exact distance transform over the union of the two row ranges with
+ * the feature test label == feature label, storing the query object's rows only, and the row pass, one workgroup per query
+ * row, whose maxima leave as one integer atomicMax per workgroup.  A workgroup finds its job by binary search over column
+ * 14 / 15.  A record that does not fit the images, scratch_elems or n_out is skipped on the device; which labels have a
+ * pixel is the caller's knowledge (medt_label_boxes).  No workgroup waits on another, no float atomics: the same bits on
+ * every run.  Null pointers, counts below 1 and a scratch of 0 elements are MEDT_EINVAL; geometry limits as above. */
+#define MEDT_PAIR_JOB_INTS 16
+int medt_label_boxes(const int32_t* labels, int32_t* box, int N, int H, int W, int stride, int max_count, void* stream);
+int medt_pair_hausdorff(const int32_t* la, const int32_t* lb, const int32_t* jobs, int32_t* scratch, int32_t* out, int n_jobs,
+                        int col_blocks, int row_blocks, size_t scratch_elems, int n_out, int clear_out, int N, int H, int W,
+                        void* stream);
 
 #ifdef __cplusplus
 }

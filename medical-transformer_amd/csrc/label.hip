@@ -1,6 +1,8 @@
 // label.hip -- connected-component labelling of uint8 masks on the device, the per-component tables and the table-driven
 // select pass (medt_label_* in medt_abi.h; medt_amd.ops.label / label_tables / remove_small_objects / fill_holes,
-// metrics.object_scores: object-level F1 and Dice, AJI, PQ; not in the reference, whose users label on the host).
+// metrics.object_scores: object-level F1 and Dice, AJI, PQ; not in the reference, whose users label on the host), and further
+// down the bounding boxes of the components and the directed squared Hausdorff distances of pairs of them (medt_label_boxes,
+// medt_pair_hausdorff; metrics.object_hausdorff: the object-level Hausdorff distance of GlaS).
 //
 // Labelling is a union-find over the pixels of the labelled set (mask != 0, or mask == 0 in background mode); a node's parent
 // is always a pixel index that is not larger than its own, so every chain of parents strictly decreases and ends in the
@@ -31,6 +33,8 @@ struct alignas(16) LabelQuad {
 // The CPU lane emulator's HIP vocabulary (tests/lane_emu) has atomicAdd and atomicOr but no atomicMin.  One work-item runs at
 // a time there, so a read-modify-write is atomic by construction.
 static inline int atomicMin(int* p, int v) { const int o = *p; *p = o < v ? o : v; return o; }
+static inline int atomicMax(int* p, int v) { const int o = *p; *p = o > v ? o : v; return o; }
+static inline int atomicCAS(int* p, int expected, int v) { const int o = *p; if (o == expected) *p = v; return o; }
 #endif
 
 // A parent that another work-item may be changing in the same launch: never from a register copy or (global memory) from
@@ -444,6 +448,217 @@ int label_select(const int32_t* labels, const uint8_t* keep, const uint8_t* mask
     if (vec) hipLaunchKernelGGL((label_select_kernel<true>), grid, block, 0, s, labels, keep, mask, out, H * W, cpi, stride);
     else hipLaunchKernelGGL((label_select_kernel<false>), grid, block, 0, s, labels, keep, mask, out, H * W, cpi, stride);
     return launch_status("label_select");
+}
+
+// ---- bounding boxes ----------------------------------------------------------------------------------------------------------
+// box[n, l] = (y0, x0, y1, x1), inclusive, of label l >= 1; (H, W, -1, -1) for a label without a pixel (what the init kernel
+// writes into every slot; slot 0 is never touched again).  Integer atomicMin / atomicMax only, so the order does not matter.
+// Per workgroup the boxes are first reduced in LDS: BOX_SLOTS direct-mapped slots keyed by label % BOX_SLOTS, claimed with a
+// compare-and-swap; a label that finds its slot taken by another label goes to the global table directly.  Nobody waits:
+// losing the claim is an answer, not a retry.  A run of one label inside a work-item's four pixels is one update.
+constexpr int BOX_SLOTS = MEDT_THREADS;
+
+__global__ __launch_bounds__(MEDT_THREADS) void label_boxes_init_kernel(int32_t* __restrict__ box, int H, int W, int total) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;      // one int32 of the (N, stride, 4) table
+    if (i < total) box[i] = (i & 3) == 0 ? H : ((i & 3) == 1 ? W : -1);
+}
+
+__device__ __forceinline__ void label_box_put(int* owner, int (*lb)[BOX_SLOTS], int32_t* __restrict__ gbox, int l, int y0, int x0,
+                                              int y1, int x1) {
+    const int slot = l % BOX_SLOTS;
+    const int old = atomicCAS(owner + slot, 0, l);
+    if (old == 0 || old == l) {
+        atomicMin(&lb[0][slot], y0); atomicMin(&lb[1][slot], x0); atomicMax(&lb[2][slot], y1); atomicMax(&lb[3][slot], x1);
+    } else {
+        int32_t* b = gbox + (size_t)l * 4;
+        atomicMin(b + 0, y0); atomicMin(b + 1, x0); atomicMax(b + 2, y1); atomicMax(b + 3, x1);
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(MEDT_THREADS) void label_boxes_kernel(const int32_t* __restrict__ labels, int32_t* __restrict__ box,
+                                                                   int H, int W, int cpi, int stride) {
+    MEDT_STATIC_SHARED int owner[BOX_SLOTS];
+    MEDT_STATIC_SHARED int lb[4][BOX_SLOTS];
+    const int HW = H * W;
+    const int n = blockIdx.x / cpi, p0 = (blockIdx.x - n * cpi) * LABEL_CHUNK + threadIdx.x * 4;
+    const size_t base = (size_t)n * HW;
+    int32_t* gbox = box + (size_t)n * stride * 4;
+    owner[threadIdx.x] = 0;
+    lb[0][threadIdx.x] = H; lb[1][threadIdx.x] = W; lb[2][threadIdx.x] = -1; lb[3][threadIdx.x] = -1;
+    __syncthreads();
+    if (p0 < HW) {
+        int a[4] = {-1, -1, -1, -1};
+        if (VEC) {
+            label_load_i32<4>(labels + base + p0, a);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (p0 + e < HW) a[e] = labels[base + p0 + e];
+        }
+        int run_label = 0, y0 = 0, x0 = 0, y1 = 0, x1 = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int l = a[e];
+            if (p0 + e >= HW || l < 1 || l >= stride) continue;
+            const int y = (p0 + e) / W, x = (p0 + e) - y * W;
+            if (l != run_label) {
+                if (run_label) label_box_put(owner, lb, gbox, run_label, y0, x0, y1, x1);
+                run_label = l; y0 = y1 = y; x0 = x1 = x;
+            } else {
+                y0 = min(y0, y); y1 = max(y1, y); x0 = min(x0, x); x1 = max(x1, x);
+            }
+        }
+        if (run_label) label_box_put(owner, lb, gbox, run_label, y0, x0, y1, x1);
+    }
+    __syncthreads();
+    const int l = owner[threadIdx.x];
+    if (l) {
+        int32_t* b = gbox + (size_t)l * 4;
+        atomicMin(b + 0, lb[0][threadIdx.x]); atomicMin(b + 1, lb[1][threadIdx.x]);
+        atomicMax(b + 2, lb[2][threadIdx.x]); atomicMax(b + 3, lb[3][threadIdx.x]);
+    }
+}
+
+int label_boxes(const int32_t* labels, int32_t* box, int N, int H, int W, int stride, hipStream_t s) {
+    const dim3 block(MEDT_THREADS);
+    const int total = N * stride * 4;                          // (the host has refused a table of 2^31 int32 or more)
+    hipLaunchKernelGGL(label_boxes_init_kernel, dim3((unsigned)cdiv(total, MEDT_THREADS)), block, 0, s, box, H, W, total);
+    const bool vec = (W % 4 == 0) && ((uintptr_t)labels % 16 == 0);
+    const int cpi = label_chunks(H, W);
+    const dim3 grid((unsigned)N * cpi);
+    if (vec) hipLaunchKernelGGL((label_boxes_kernel<true>), grid, block, 0, s, labels, box, H, W, cpi, stride);
+    else hipLaunchKernelGGL((label_boxes_kernel<false>), grid, block, 0, s, labels, box, H, W, cpi, stride);
+    return launch_status("label_boxes");
+}
+
+// ---- directed squared Hausdorff distances of pairs of components ----------------------------------------------------------------
+// A JOB is one pair and one direction: a query object (label q of one map) and a feature object (label f of the other).  Its
+// result, max over the query's pixels of the squared distance to the nearest feature pixel, comes from the two-pass transform
+// of elementwise.hip cut down to the job's crop:
+//   columns  one work-item per column of the feature object's column range sweeps the UNION of the two objects' row ranges
+//            down and up with the feature test label == f and writes the squared vertical distances of the QUERY's rows only:
+//            the job's g2 is query rows x feature columns of scratch
+//   rows     one workgroup per query row with that row of g2 in LDS; a work-item runs the outward search of edt_rows_kernel
+//            from every pixel of the row with label == q (which may lie outside the feature's columns: the search then starts
+//            at the nearest of them), the maxima are reduced per wave and per workgroup and leave as ONE atomicMax per
+//            workgroup into out[job's slot]
+// Jobs come as a device table of PH_JOB int32 each (medt_abi.h) whose `first block' columns are the prefix sums of the
+// blocks the jobs before it take in either launch: a workgroup finds its job by binary search over them.  A job whose
+// fields do not fit the images, the scratch or `out' is skipped by both kernels (a check per workgroup, on scalars): the
+// table is device memory the host side of this call cannot read.  Integers throughout, integer max: the same bits on every
+// run; nobody waits on another workgroup.
+constexpr int PH_JOB = MEDT_PAIR_JOB_INTS;
+constexpr int PH_FAR = 1 << 30;               // what the row pass holds in LDS for MEDT_EDT_NONE: PH_FAR + 4095^2 < 2^31
+enum { PH_N, PH_QLAB, PH_FLAB, PH_SWAP, PH_QY0, PH_QY1, PH_QX0, PH_QX1, PH_FX0, PH_FX1, PH_SY0, PH_SY1, PH_OFF, PH_OUT, PH_COLB, PH_ROWB };
+
+struct PairJob {
+    int n, qlab, flab, swap, qy0, qy1, qx0, qx1, fx0, fx1, sy0, sy1, off, out, first;
+    bool ok;
+};
+
+// the last job whose first block is <= blk (the prefix is non-decreasing and starts at 0), and its fields
+__device__ __forceinline__ PairJob pair_job(const int32_t* __restrict__ jobs, int n_jobs, int which, int blk, int N, int H, int W,
+                                            long long scratch_elems, int n_out) {
+    int lo = 0, hi = n_jobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[(size_t)mid * PH_JOB + which] <= blk) lo = mid; else hi = mid - 1;
+    }
+    const int32_t* j = jobs + (size_t)lo * PH_JOB;
+    PairJob r;
+    r.n = j[PH_N]; r.qlab = j[PH_QLAB]; r.flab = j[PH_FLAB]; r.swap = j[PH_SWAP];
+    r.qy0 = j[PH_QY0]; r.qy1 = j[PH_QY1]; r.qx0 = j[PH_QX0]; r.qx1 = j[PH_QX1];
+    r.fx0 = j[PH_FX0]; r.fx1 = j[PH_FX1]; r.sy0 = j[PH_SY0]; r.sy1 = j[PH_SY1];
+    r.off = j[PH_OFF]; r.out = j[PH_OUT]; r.first = j[which];
+    r.ok = r.n >= 0 && r.n < N && r.qlab >= 1 && r.flab >= 1 && r.qy0 >= 0 && r.qy0 <= r.qy1 && r.qy1 < H && r.qx0 >= 0 &&
+           r.qx0 <= r.qx1 && r.qx1 < W && r.fx0 >= 0 && r.fx0 <= r.fx1 && r.fx1 < W && r.sy0 >= 0 && r.sy0 <= r.qy0 &&
+           r.qy1 <= r.sy1 && r.sy1 < H && r.off >= 0 && r.out >= 0 && r.out < n_out && r.first <= blk &&
+           (long long)r.off + (long long)(r.qy1 - r.qy0 + 1) * (r.fx1 - r.fx0 + 1) <= scratch_elems;
+    return r;
+}
+
+__global__ __launch_bounds__(MEDT_THREADS) void pair_cols_kernel(const int32_t* __restrict__ la, const int32_t* __restrict__ lb,
+                                                                 const int32_t* __restrict__ jobs, int32_t* __restrict__ scratch,
+                                                                 int n_jobs, int N, int H, int W, long long scratch_elems, int n_out) {
+    const PairJob j = pair_job(jobs, n_jobs, PH_COLB, (int)blockIdx.x, N, H, W, scratch_elems, n_out);
+    if (!j.ok) return;
+    const int fw = j.fx1 - j.fx0 + 1;
+    const int c = ((int)blockIdx.x - j.first) * MEDT_THREADS + (int)threadIdx.x;         // column of the crop
+    if (c >= fw) return;
+    const int32_t* f = (j.swap ? la : lb) + (size_t)j.n * H * W + (j.fx0 + c);
+    int32_t* g = scratch + (size_t)j.off + c;
+    int dist = MEDT_EDT_NONE;
+    for (int y = j.sy0; y <= j.sy1; ++y) {                     // down: the nearest feature pixel at or above
+        dist = f[(size_t)y * W] == j.flab ? 0 : (dist == MEDT_EDT_NONE ? MEDT_EDT_NONE : dist + 1);
+        if (y >= j.qy0 && y <= j.qy1) g[(size_t)(y - j.qy0) * fw] = dist;
+    }
+    dist = MEDT_EDT_NONE;
+    for (int y = j.sy1; y >= j.sy0; --y) {                     // up: the one below, the smaller of the two squared
+        if (y >= j.qy0 && y <= j.qy1) {
+            int32_t* p = g + (size_t)(y - j.qy0) * fw;
+            const int a = *p;
+            dist = a == 0 ? 0 : (dist == MEDT_EDT_NONE ? MEDT_EDT_NONE : dist + 1);
+            const int d = min(a, dist);
+            *p = d == MEDT_EDT_NONE ? MEDT_EDT_NONE : d * d;
+        } else {
+            dist = f[(size_t)y * W] == j.flab ? 0 : (dist == MEDT_EDT_NONE ? MEDT_EDT_NONE : dist + 1);
+        }
+    }
+}
+
+__global__ __launch_bounds__(MEDT_THREADS) void pair_rows_kernel(const int32_t* __restrict__ la, const int32_t* __restrict__ lb,
+                                                                 const int32_t* __restrict__ jobs, const int32_t* __restrict__ scratch,
+                                                                 int32_t* __restrict__ out, int n_jobs, int N, int H, int W,
+                                                                 long long scratch_elems, int n_out) {
+    MEDT_STATIC_SHARED int gs[MEDT_LABEL_MAX_DIM];
+    MEDT_STATIC_SHARED int red[MEDT_THREADS / 64];
+    const PairJob j = pair_job(jobs, n_jobs, PH_ROWB, (int)blockIdx.x, N, H, W, scratch_elems, n_out);
+    if (!j.ok) return;                                         // (uniform over the workgroup: nobody is left at a barrier)
+    const int r = (int)blockIdx.x - j.first;
+    if (r > j.qy1 - j.qy0) return;
+    const int fw = j.fx1 - j.fx0 + 1, y = j.qy0 + r, tid = threadIdx.x;
+    const int32_t* g = scratch + (size_t)j.off + (size_t)r * fw;
+    for (int i = tid; i < fw; i += MEDT_THREADS) gs[i] = min(g[i], PH_FAR);
+    __syncthreads();
+    const int32_t* q = (j.swap ? lb : la) + ((size_t)j.n * H + y) * W;
+    int worst = 0;
+    for (int x = j.qx0 + tid; x <= j.qx1; x += MEDT_THREADS) {
+        if (q[x] != j.qlab) continue;
+        int best = PH_FAR;
+        const int reach = max(x - j.fx0, j.fx1 - x);           // the farthest feature column
+        for (int d = max(0, max(j.fx0 - x, x - j.fx1)); d <= reach; ++d) {     // from the nearest one outwards, both sides at once
+            const int dd = d * d;
+            if (dd >= best) break;
+            const int xl = x - d, xr = x + d;
+            if (xl >= j.fx0 && xl <= j.fx1) best = min(best, gs[xl - j.fx0] + dd);
+            if (xr >= j.fx0 && xr <= j.fx1) best = min(best, gs[xr - j.fx0] + dd);
+        }
+        if (best >= PH_FAR) best = MEDT_EDT_NONE;              // a feature object without a pixel (the host refuses such a pair)
+        worst = max(worst, best);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) worst = max(worst, __shfl_xor(worst, o, 64));
+    if ((tid & 63) == 0) red[tid >> 6] = worst;
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < MEDT_THREADS / 64; ++w) worst = max(worst, red[w]);
+        if (worst > 0) atomicMax(out + j.out, worst);          // (out starts at 0 and distances are >= 0)
+    }
+}
+
+int pair_hausdorff(const int32_t* la, const int32_t* lb, const int32_t* jobs, int32_t* scratch, int32_t* out, int n_jobs,
+                   int col_blocks, int row_blocks, size_t scratch_elems, int n_out, int clear_out, int N, int H, int W, hipStream_t s) {
+    if (clear_out && hipMemsetAsync(out, 0, (size_t)n_out * sizeof(int32_t), s) != hipSuccess) {
+        set_error("pair_hausdorff: clearing out failed"); return MEDT_ELAUNCH;
+    }
+    const dim3 block(MEDT_THREADS);
+    hipLaunchKernelGGL(pair_cols_kernel, dim3((unsigned)col_blocks), block, 0, s, la, lb, jobs, scratch, n_jobs, N, H, W,
+                       (long long)scratch_elems, n_out);
+    hipLaunchKernelGGL(pair_rows_kernel, dim3((unsigned)row_blocks), block, 0, s, la, lb, jobs, scratch, out, n_jobs, N, H, W,
+                       (long long)scratch_elems, n_out);
+    return launch_status("pair_hausdorff");
 }
 
 }  // namespace medt

@@ -1084,6 +1084,32 @@ int medt_label_select(const int32_t* labels, const uint8_t* keep, const uint8_t*
     return label_select(labels, keep, mask, out, N, H, W, stride, (hipStream_t)stream);
 }
 
+int medt_label_boxes(const int32_t* labels, int32_t* box, int N, int H, int W, int stride, int max_count, void* stream) {
+    if (const int rc = label_geometry("label_boxes", N, H, W)) return rc;
+    if (!labels || !box) { set_error("label_boxes: null labels or box"); return MEDT_EINVAL; }
+    if (max_count < 0 || stride <= max_count) {
+        set_error("label_boxes: stride %d cannot hold the labels 0..%d", stride, max_count); return MEDT_EINVAL;
+    }
+    if ((size_t)N * stride * 4 >= ((size_t)1 << 31)) {
+        set_error("label_boxes: %d tables of %d boxes: 2^31 elements or more", N, stride); return MEDT_EUNSUPPORTED;
+    }
+    return label_boxes(labels, box, N, H, W, stride, (hipStream_t)stream);
+}
+
+int medt_pair_hausdorff(const int32_t* la, const int32_t* lb, const int32_t* jobs, int32_t* scratch, int32_t* out, int n_jobs,
+                        int col_blocks, int row_blocks, size_t scratch_elems, int n_out, int clear_out, int N, int H, int W,
+                        void* stream) {
+    if (const int rc = label_geometry("pair_hausdorff", N, H, W)) return rc;
+    if (!la || !lb || !jobs || !scratch || !out) { set_error("pair_hausdorff: null label map, jobs, scratch or out"); return MEDT_EINVAL; }
+    if (n_jobs < 1 || col_blocks < n_jobs || row_blocks < n_jobs || n_out < 1 || scratch_elems < 1) {
+        set_error("pair_hausdorff: %d jobs in %d + %d blocks, %zu scratch elements, %d results", n_jobs, col_blocks, row_blocks,
+                  scratch_elems, n_out);
+        return MEDT_EINVAL;
+    }
+    return pair_hausdorff(la, lb, jobs, scratch, out, n_jobs, col_blocks, row_blocks, scratch_elems, n_out, clear_out, N, H, W,
+                          (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 #ifdef MEDT_LANE_EMU

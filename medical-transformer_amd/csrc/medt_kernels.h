@@ -139,6 +139,10 @@ int label_components(const uint8_t* mask, int32_t* labels, int32_t* count, void*
 int label_tables(const int32_t* labels, int32_t* area, uint8_t* frame, int N, int H, int W, int stride, hipStream_t s);
 int label_select(const int32_t* labels, const uint8_t* keep, const uint8_t* mask, uint8_t* out, int N, int H, int W, int stride,
                  hipStream_t s);
+// bounding boxes of the components; directed squared Hausdorff distances of pairs of them from a device job table (label.hip)
+int label_boxes(const int32_t* labels, int32_t* box, int N, int H, int W, int stride, hipStream_t s);
+int pair_hausdorff(const int32_t* la, const int32_t* lb, const int32_t* jobs, int32_t* scratch, int32_t* out, int n_jobs,
+                   int col_blocks, int row_blocks, size_t scratch_elems, int n_out, int clear_out, int N, int H, int W, hipStream_t s);
 int logo_merge_fwd(const float* x, const float* yp, float* y, int N, int C, int S, int P, int G, hipStream_t s);
 int logo_merge_bwd(const float* dy, float* dx, float* dyp, int N, int C, int S, int P, int G, hipStream_t s);
 int ce_parts(size_t npix);

@@ -161,6 +161,8 @@ SIGNATURES = {
     "medt_label_components": (C.c_int, [C.c_void_p] * 4 + [C.c_size_t] + [C.c_int] * 5 + [C.c_void_p]),
     "medt_label_tables": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
     "medt_label_select": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "medt_label_boxes": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
+    "medt_pair_hausdorff": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_size_t] + [C.c_int] * 5 + [C.c_void_p]),
 }
 
 

@@ -773,3 +773,107 @@ def label_overlaps(la, ca, lb, cb):
     both = (a > 0) & (b > 0)
     key, cnt = torch.unique(((n * sa + a) * sb + b)[both], return_counts=True)          # (sorted)
     return torch.stack([key // (sa * sb), key // sb % sa, key % sb, cnt], dim=1)
+
+
+# --------------------------------------------------------------------------- #
+# bounding boxes and per-pair directed Hausdorff distances (metrics.object_hausdorff)
+# --------------------------------------------------------------------------- #
+PAIR_JOB_INTS = 16                 # MEDT_PAIR_JOB_INTS of include/medt_abi.h: int32 per record of the job table
+PAIR_THREADS = 256                 # work-items of a workgroup: a job takes ceil(feature columns / 256) blocks of the column launch
+PAIR_SCRATCH_ELEMS = 1 << 24       # default bound of the scratch of one chunk of jobs, in int32 elements (64 MiB): the g2 of one
+                                   # whole 4096 x 4096 map, the largest a single job can need, so no job ever exceeds the default
+
+
+def label_boxes(labels, counts):
+    """Label map (N,H,W) or (H,W) int32 and its counts (N,) -> int32 (N, stride, 4) with stride = counts.max() + 1 (one host
+    sync): (y0, x0, y1, x1), inclusive, of every label; (H, W, -1, -1) for a label without a pixel and for slot 0."""
+    lab, cnt = _label_maps("label_boxes", labels, counts)
+    N, H, W = lab.shape
+    top = int(cnt.max())
+    stride = top + 1
+    box = torch.empty(N, stride, 4, device=lab.device, dtype=torch.int32)
+    L.check(L.lib().medt_label_boxes(lab.data_ptr(), box.data_ptr(), N, H, W, stride, top, _stream()), "medt_label_boxes")
+    return box
+
+
+def _pair_chunks(sizes, budget):
+    """Greedy cut of the jobs, in order, into chunks [start, end) whose summed sizes stay at or below budget; a job larger than
+    the budget is a chunk of its own."""
+    cum = torch.cumsum(sizes, 0)
+    chunks, start, J = [], 0, sizes.numel()
+    while start < J:
+        before = int(cum[start - 1]) if start else 0
+        end = int(torch.searchsorted(cum, torch.tensor(before + budget), right=True))
+        end = max(end, start + 1)
+        chunks.append((start, end))
+        start = end
+    return chunks
+
+
+def pair_hausdorff_sq(la, ca, lb, cb, pairs, max_scratch_elems=None, boxes=None):
+    """Two label maps of one shape with their counts and int32 (M,3) rows (n, a, b) -> int32 (M,2) on the maps' device:
+      [:,0] = max over the pixels x of object a of la[n] of min over the pixels y of object b of lb[n] of |x - y|^2,
+      [:,1] = the same from b to a,
+    exact integers over ALL pixels of both objects (the two directed squared Hausdorff distances of the pair).  A pair that
+    names a label outside 1..count or one without a pixel is refused (MEDT_EINVAL), on the host, from the bounding boxes.
+    Every pair is two jobs (one per direction) of a device job table; a job's scratch is (rows of the query object's box) x
+    (columns of the feature object's box) int32, and the jobs are issued in chunks whose summed scratch stays at or below
+    max_scratch_elems (default PAIR_SCRATCH_ELEMS); a job that alone is larger runs alone.  boxes: (label_boxes(la, ca),
+    label_boxes(lb, cb)) when the caller has them already, on any device."""
+    A, ca = _label_maps("pair_hausdorff_sq", la, ca)
+    B, cb = _label_maps("pair_hausdorff_sq", lb, cb)
+    if A.shape != B.shape or A.device != B.device:
+        raise L.MedtError("pair_hausdorff_sq: label maps of one shape on one device expected")
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 3:
+        raise L.MedtError("pair_hausdorff_sq: pairs must be int32 (M,3) rows (n, a, b)")
+    N, H, W = A.shape
+    M = pairs.shape[0]
+    out = torch.empty(M, 2, device=A.device, dtype=torch.int32)      # (the first call below zeroes it)
+    if M == 0:
+        return out
+    budget = PAIR_SCRATCH_ELEMS if max_scratch_elems is None else int(max_scratch_elems)
+    if budget < 1:
+        raise L.MedtError(f"pair_hausdorff_sq: max_scratch_elems {max_scratch_elems!r} (at least 1)")
+    budget = min(budget, 2 ** 31 - 1)
+    ba, bb = boxes if boxes is not None else (label_boxes(A, ca), label_boxes(B, cb))
+    ba, bb = torch.as_tensor(ba).cpu().long().reshape(N, -1, 4), torch.as_tensor(bb).cpu().long().reshape(N, -1, 4)
+    p = torch.as_tensor(pairs).cpu().long()
+    n, a, b = p[:, 0], p[:, 1], p[:, 2]
+    if bool(((n < 0) | (n >= N)).any()):
+        raise L.MedtError(f"pair_hausdorff_sq failed (-1): an image index outside 0..{N - 1}")
+    if bool(((a < 1) | (a >= ba.shape[1]) | (b < 1) | (b >= bb.shape[1])).any()):
+        raise L.MedtError("pair_hausdorff_sq failed (-1): a pair names a label outside 1..count")
+    qa, qb = ba[n, a], bb[n, b]                                    # (M,4) boxes y0, x0, y1, x1
+    if bool(((qa[:, 2] < 0) | (qb[:, 2] < 0)).any()):
+        bad = int(torch.nonzero((qa[:, 2] < 0) | (qb[:, 2] < 0))[0])
+        raise L.MedtError(f"pair_hausdorff_sq failed (-1): pair {p[bad].tolist()} names a label without a pixel")
+    # two jobs per pair, interleaved: 2m is a -> b (query in la), 2m + 1 is b -> a (query in lb)
+    J = 2 * M
+    q = torch.stack([qa, qb], 1).reshape(J, 4)                     # the query object's box
+    f = torch.stack([qb, qa], 1).reshape(J, 4)                     # the feature object's
+    table = torch.zeros(J, PAIR_JOB_INTS, dtype=torch.int64)
+    table[:, 0] = n.repeat_interleave(2)
+    table[:, 1] = torch.stack([a, b], 1).reshape(J)
+    table[:, 2] = torch.stack([b, a], 1).reshape(J)
+    table[:, 3] = torch.arange(J) % 2
+    table[:, 4], table[:, 5], table[:, 6], table[:, 7] = q[:, 0], q[:, 2], q[:, 1], q[:, 3]
+    table[:, 8], table[:, 9] = f[:, 1], f[:, 3]
+    table[:, 10], table[:, 11] = torch.minimum(q[:, 0], f[:, 0]), torch.maximum(q[:, 2], f[:, 2])
+    table[:, 13] = torch.arange(J)
+    rows = q[:, 2] - q[:, 0] + 1
+    cols = f[:, 3] - f[:, 1] + 1
+    sizes = rows * cols
+    colb = (cols + PAIR_THREADS - 1) // PAIR_THREADS
+    chunks = _pair_chunks(sizes, budget)
+    scratch = torch.empty(max(int(sizes[s:e].sum()) for s, e in chunks), device=A.device, dtype=torch.int32)
+    lib = L.lib()
+    for k, (s, e) in enumerate(chunks):
+        t = table[s:e].clone()
+        t[:, 12] = torch.cumsum(sizes[s:e], 0) - sizes[s:e]
+        t[:, 14] = torch.cumsum(colb[s:e], 0) - colb[s:e]
+        t[:, 15] = torch.cumsum(rows[s:e], 0) - rows[s:e]
+        jobs = t.to(torch.int32).to(A.device)
+        L.check(lib.medt_pair_hausdorff(A.data_ptr(), B.data_ptr(), jobs.data_ptr(), scratch.data_ptr(), out.data_ptr(), e - s,
+                                        int(colb[s:e].sum()), int(rows[s:e].sum()), scratch.numel(), J, int(k == 0), N, H, W,
+                                        _stream()), "medt_pair_hausdorff")
+    return out

@@ -4,7 +4,8 @@ train.py (with or without DataParallel's "module." prefix), runs the network in 
 thresholded channel-1 prediction of every validation image as <direc>/<filename>.  The reference reads an
 undefined args.aug (test.py:62) and dies; here the flag exists and is ignored.  --surface on adds the surface-distance scores
 (HD, HD95, ASSD) of the written masks behind the F1 / mIoU / PA line, --objects on the object-level scores (object F1 and Dice,
-AJI, PQ) behind those; --fill_holes on and --min_object AREA clean the masks on the device before they are written and scored."""
+AJI, PQ) behind those, --object_hausdorff on the object-level Hausdorff distance of GlaS behind those; --fill_holes on and
+--min_object AREA clean the masks on the device before they are written and scored."""
 import argparse
 import os
 
@@ -56,8 +57,14 @@ parser.add_argument('--objects', default='off', choices=['off', 'on'],
                          'the label maps -- GlaS object F1 and object Dice, Aggregated Jaccard Index, panoptic quality -- means over '
                          'the images in which the mask or the label map has an object (metrics.object_scores: connected-component '
                          'labelling on the device)')
+parser.add_argument('--object_hausdorff', default='off', choices=['off', 'on'],
+                    help='(not in the reference) on: a further score line with the object-level Hausdorff distance of GlaS of the '
+                         'written masks against the label maps, in pixels, averaged over the images in which both the mask and '
+                         'the label map have an object (metrics.object_hausdorff: labelling and one distance transform per '
+                         'object pair on the device); prints only its own line, --objects is not needed')
 parser.add_argument('--connectivity', type=int, default=8, choices=[4, 8],
-                    help="(not in the reference) connectivity of the objects of --objects and --min_object (8: MATLAB's bwlabel)")
+                    help="(not in the reference) connectivity of the objects of --objects, --object_hausdorff and --min_object "
+                         "(8: MATLAB's bwlabel)")
 parser.add_argument('--min_object', type=int, default=0, metavar='AREA',
                     help='(not in the reference) > 0: objects of fewer than AREA pixels are removed from every mask before it is '
                          'written and scored (medt_amd.ops.remove_small_objects)')
@@ -93,6 +100,8 @@ def main():
     scores = []
     surface = [] if args.surface == "on" else None     # per-batch metrics.surface_scores of (mask, target > 0), eager, behind the replay
     objects = [] if args.objects == "on" else None     # per-batch metrics.object_scores of the same pairs
+    obj_hd = [] if args.object_hausdorff == "on" else None   # per-batch metrics.object_hausdorff of the same pairs
+    scoring = surface is not None or objects is not None or obj_hd is not None
     cleaning = args.fill_holes == "on" or args.min_object > 0
 
     def clean(mask, target, like):
@@ -113,6 +122,8 @@ def main():
             surface.append(metrics.surface_scores(mask, t))
         if objects is not None:
             objects.append(metrics.object_scores(mask, t, args.connectivity))
+        if obj_hd is not None:
+            obj_hd.append(metrics.object_hausdorff(mask, t, args.connectivity))
 
     # forward + the device-side counts as ONE replayed hipGraph per image shape (medt_amd.trainer.InferStep): an eager
     # forward is ~110 dependent launches issued from Python and is host-bound
@@ -134,7 +145,7 @@ def main():
                 imwrite(fulldir + it[2], mask[k])
             return
         scores.append(counts[:len(items)].clone())
-        if surface is not None or objects is not None:   # the mask the PNG holds (same comparison, on the device) against target > 0
+        if scoring:   # the mask the PNG holds (same comparison, on the device) against target > 0
             score((y_out[:len(items), 1] >= 0.5).to(torch.uint8) * 255, ys[:len(items)])
         yHaT = (y_out[:len(items)].detach().cpu().numpy() >= 0.5).astype(np.uint8) * 255
         for k, it in enumerate(items):
@@ -155,7 +166,7 @@ def main():
                 mask, counts = clean(mask.unsqueeze(0), target, counts)
                 mask = mask[0]
             scores.append(counts)
-            if surface is not None or objects is not None:
+            if scoring:
                 score(mask.unsqueeze(0), target)
             imwrite(fulldir + image_filename, mask.cpu().numpy())
         valloader = ()
@@ -184,6 +195,11 @@ def main():
         f1o, diceo, aji, pq = (torch.cat([s[k] for s in objects])[valid] for k in ("f1", "dice", "aji", "pq"))
         print("objects images {}/{}  F1obj {:.4f}  Diceobj {:.4f}  AJI {:.4f}  PQ {:.4f}".format(
             int(valid.sum()), len(valid), *(v.mean().item() if len(v) else float("nan") for v in (f1o, diceo, aji, pq))))
+    if obj_hd:
+        valid = torch.cat([s["valid"] for s in obj_hd])
+        hobj = torch.cat([s["hd"] for s in obj_hd])[valid]
+        print("object hausdorff images {}/{}  Hobj {:.4f}".format(int(valid.sum()), len(valid),
+                                                                  hobj.mean().item() if len(hobj) else float("nan")))
 
 
 if __name__ == "__main__":
