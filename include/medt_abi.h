@@ -39,7 +39,8 @@ extern "C" {
  * entry points were added under the same number: additions only, nothing that version 11 declared was removed or changed,
  * so a caller built against the earlier header keeps working.  The medt_label_* entry points were added under the same
  * number: additions only, nothing that version 11 declared was removed or changed, so a caller built against the earlier
- * header keeps working.  medt_label_boxes and medt_pair_hausdorff were added under the same number, in the same way. */
+ * header keeps working.  medt_label_boxes and medt_pair_hausdorff were added under the same number, in the same way.
+ * medt_signed_edt and the medt_boundary_* entry points were added under the same number, in the same way. */
 #define MEDT_ABI_VERSION 11
 
 #define MEDT_OK            0
@@ -455,6 +456,40 @@ int medt_augment_apply(const uint8_t* image, const uint8_t* mask, const float* p
 #define MEDT_EDT_MAX_DIM 4096
 int medt_edt_cols(const uint8_t* mask, int32_t* g2, int N, int H, int W, int border_mode, void* stream);
 int medt_edt_rows(const int32_t* g2, const uint8_t* select, int32_t* d2, int N, int H, int W, void* stream);
+
+/* Boundary loss of the training step (Kervadec et al., "Boundary loss for highly unbalanced segmentation", MIDL 2019): the
+ * signed distance map of the label map the step holds on the device, and the term built on it.
+ *
+ * medt_signed_edt: target (N,H,W) int64 class indices -> sd2 (N,H,W) int32, in two launches (columns, rows).  The foreground
+ * F is {target == fg} (fg >= 0; a pixel equal to ignore_index is never in F); every other pixel -- ignored, out of range, any
+ * other class -- is outside F.  Outside F sd2 = +d^2 to the nearest pixel of F (>= 1), inside F sd2 = -d^2 to the nearest pixel
+ * outside F (<= -1); an image without a pixel of F holds 0 everywhere, and so does an image that is all F.  g2: N*H*W int32 of
+ * scratch (the signed column map: > 0 outside F, < 0 inside, see elementwise.hip), must not alias sd2.  Exact: integers
+ * throughout, no atomics, bit-identical from run to run.  Element accesses only: no alignment beyond the elements' own.
+ * Limits as medt_edt_*: 1 <= H, W <= MEDT_EDT_MAX_DIM, N*H*W below 2^31 (MEDT_EUNSUPPORTED beyond, before any launch).
+ *
+ * medt_boundary_fwd / _bwd: logits (N,K,HW) float32, target (N,HW) int64, sd2 (N,HW) from medt_signed_edt; K >= 2, 0 <= fg < K.
+ *   s = softmax(logits)[fg];  phi = sqrt(sd2) where sd2 > 0, -(sqrt(-sd2) - 1) where sd2 < 0, 0 where sd2 == 0 (computed on the
+ *   fly, never stored);  B = mean over images n of ( sum over the valid pixels p of phi_n(p) s_n(p) / max(1, V_n) ), V_n the
+ *   number of valid pixels of image n; a pixel is valid when its target is in [0, K) and is not ignore_index.
+ * alpha: ONE float32 in device memory, read on the device when the kernels run (the finalize reads it and hands it on in
+ * out[2], where the backward of the same step reads it) -- a captured step follows a schedule that refills it in place; no
+ * launch argument depends on its value.  base: NULL, or one device float (the region loss, out[0] of
+ * medt_seg_loss_fwd / loss_out[0] of medt_ce_fwd).
+ *   out: medt_boundary_out_floats(N) floats = [base + alpha B (alpha B when base is NULL), B, alpha as read,
+ *   1 / (N max(1, V_n)) for n < N];  partials: medt_boundary_workspace(N, HW) floats.  fwd is two launches (partial sums, one
+ *   finalize in double), bwd one; every sum has a fixed order, no float atomics.
+ *   bwd: dlogits[n,k,p] = dloss alpha phi / (N max(1, V_n)) s (delta(k,fg) - p_k) at the valid pixels (dloss: one device float,
+ *   NULL = 1).  accumulate == 0 writes dlogits, zeros at the pixels that are not valid included; accumulate != 0 ADDS into the
+ *   dlogits that medt_seg_loss_bwd / medt_ce_bwd has just written for the same logits and targets (which holds the zeros
+ *   already): one gradient buffer for region + boundary term. */
+int medt_signed_edt(const int64_t* target, int32_t* g2, int32_t* sd2, int N, int H, int W, int fg, int ignore_index, void* stream);
+size_t medt_boundary_workspace(int N, int HW);
+size_t medt_boundary_out_floats(int N);
+int medt_boundary_fwd(const float* logits, const int64_t* target, const int32_t* sd2, const float* alpha, const float* base,
+                      float* partials, float* out, int N, int K, int HW, int fg, int ignore_index, void* stream);
+int medt_boundary_bwd(const float* logits, const int64_t* target, const int32_t* sd2, const float* out, const float* dloss,
+                      float* dlogits, int N, int K, int HW, int fg, int ignore_index, int accumulate, void* stream);
 
 /* Connected-component labelling of binary masks on the device, the per-component tables and a table-driven select pass -- the
  * building blocks of the object-level scores (metrics.object_scores: GlaS object F1 / Dice, AJI, PQ) and of the two mask

@@ -1603,4 +1603,257 @@ int edt_rows(const int32_t* g2, const uint8_t* select, int32_t* d2, int N, int H
     return launch_status("edt_rows");
 }
 
+// --------------------------------------------------------------------------- //
+// Signed squared distance map of a label map, for the boundary loss of the training step (Kervadec et al., MIDL 2019):
+//   F = {target == fg};  sd2 = +d^2 to the nearest pixel of F outside F, -d^2 to the nearest pixel outside F inside it,
+//   0 everywhere in an image that has no F pixel or no other pixel.
+// The training-path sibling of the transform above: class indices in, small maps (4 x 128^2 in a step), two launches.
+// Column pass: the distance along the column to the nearest F pixel is wanted at the pixels outside F and is 0 inside; the
+// distance to the nearest pixel outside F is wanted inside F and is 0 outside.  The two maps never both hold a value at one
+// pixel, so they share one int32 word: g2 > 0 outside F (the first map), g2 < 0 inside (minus the second), +-EDT_FAR where the
+// column has no pixel of the other set.  The row pass reads the query pixel's own set from the sign of its own word and takes
+// max(+-g2, 0) as the column term of the others.
+// A column is cut into words of 32 rows; a work-item owns one word of one column, EDT_SCOLS neighbouring columns side by side
+// in the lanes.  Its 32 loads are independent; the set bits go to LDS, where a word finds the nearest pixel of either set
+// above and below it in the other words of its column; inside the word the neighbours come from bit scans.  No sweep carries a
+// dependency through global memory, and 128 rows are 4 work-items deep instead of 2 x 128 dependent steps.
+// --------------------------------------------------------------------------- //
+constexpr int EDT_SCOLS = 16;                                // columns per workgroup of the signed column pass
+constexpr int EDT_SWORDS = MEDT_EDT_MAX_DIM / 32;            // 32-row words per column at most
+constexpr int EDT_SOFF = 1 << 15;                            // a row further off than any pixel: (EDT_SOFF)^2 = EDT_FAR
+
+// squared distance from row y to the nearest set bit of `other` (bits of the rows y0 .. y0+31), or to `up` / `dn`, the
+// nearest such rows outside the word (-EDT_SOFF / 2 * EDT_SOFF when there is none); EDT_FAR when the column has none
+__device__ __forceinline__ int edt_signed_col_d2(uint32_t other, int r, int y0, int up, int dn) {
+    const uint32_t below = other & ((1u << r) - 1u), above = (other >> r) >> 1;
+    const int y = y0 + r;
+    const int a = below ? y0 + 31 - __builtin_clz(below) : up;
+    const int b = above ? y + 1 + __builtin_ctz(above) : dn;
+    const int d = min(y - a, b - y);
+    return d >= EDT_SOFF ? EDT_FAR : d * d;
+}
+
+__global__ __launch_bounds__(MEDT_THREADS) void signed_edt_cols_kernel(const int64_t* __restrict__ target,
+                                                                       int32_t* __restrict__ g2, int H, int W, int tiles,
+                                                                       int words, int fg, int ignore) {
+    MEDT_STATIC_SHARED uint32_t bits[EDT_SWORDS * EDT_SCOLS];
+    const int n = blockIdx.x / tiles;
+    const int c = threadIdx.x % EDT_SCOLS, slot = threadIdx.x / EDT_SCOLS, slots = blockDim.x / EDT_SCOLS;
+    const int x = (blockIdx.x - n * tiles) * EDT_SCOLS + c;
+    const int64_t* t = target + (size_t)n * H * W + x;
+    int32_t* g = g2 + (size_t)n * H * W + x;
+    if (x < W) {
+        for (int w = slot; w < words; w += slots) {
+            const int y0 = w * 32, rows = min(32, H - y0);
+            uint32_t f = 0;
+#pragma unroll 8
+            for (int r = 0; r < rows; ++r) {
+                const int64_t v = t[(size_t)(y0 + r) * W];
+                f |= (v == fg && v != ignore) ? 1u << r : 0u;
+            }
+            bits[w * EDT_SCOLS + c] = f;
+        }
+    }
+    __syncthreads();
+    if (x >= W) return;
+    for (int w = slot; w < words; w += slots) {
+        const int y0 = w * 32, rows = min(32, H - y0);
+        const uint32_t valid = rows == 32 ? 0xffffffffu : (1u << rows) - 1u;
+        const uint32_t f = bits[w * EDT_SCOLS + c], o = ~f & valid;
+        int upF = -EDT_SOFF, upO = -EDT_SOFF, dnF = 2 * EDT_SOFF, dnO = 2 * EDT_SOFF;
+        for (int v = w - 1; v >= 0 && (upF < 0 || upO < 0); --v) {          // every word above the last is full
+            const uint32_t m = bits[v * EDT_SCOLS + c], mo = ~m;
+            if (upF < 0 && m) upF = v * 32 + 31 - __builtin_clz(m);
+            if (upO < 0 && mo) upO = v * 32 + 31 - __builtin_clz(mo);
+        }
+        for (int v = w + 1; v < words && (dnF >= EDT_SOFF || dnO >= EDT_SOFF); ++v) {
+            const int vr = min(32, H - v * 32);
+            const uint32_t m = bits[v * EDT_SCOLS + c], mo = ~m & (vr == 32 ? 0xffffffffu : (1u << vr) - 1u);
+            if (dnF >= EDT_SOFF && m) dnF = v * 32 + __builtin_ctz(m);
+            if (dnO >= EDT_SOFF && mo) dnO = v * 32 + __builtin_ctz(mo);
+        }
+#pragma unroll 8
+        for (int r = 0; r < rows; ++r) {
+            const bool in = (f >> r) & 1u;
+            const int d2 = in ? edt_signed_col_d2(o, r, y0, upO, dnO) : edt_signed_col_d2(f, r, y0, upF, dnF);
+            g[(size_t)(y0 + r) * W] = in ? -d2 : d2;
+        }
+    }
+}
+
+// Rows of the signed column map in LDS, 256 / T of them per workgroup when a row needs only T < 256 work-items (rpb; two at
+// 128 columns).  The search of edt_rows_kernel with the column term taken from the side of the query pixel's own sign.
+__global__ __launch_bounds__(MEDT_THREADS) void signed_edt_rows_kernel(const int32_t* __restrict__ g2, int32_t* __restrict__ sd2,
+                                                                       int W, int T, int rpb, int nrows) {
+    MEDT_STATIC_SHARED int32_t gs[MEDT_EDT_MAX_DIM];
+    const int rr = threadIdx.x / T, lx = threadIdx.x - rr * T;
+    const int rowi = blockIdx.x * rpb + rr;
+    const bool live = rr < rpb && rowi < nrows;
+    const size_t row = (size_t)(live ? rowi : 0) * W;
+    int32_t* my = gs + rr * T;                                  // rpb > 1 only when W <= T
+    if (live)
+        for (int x = lx; x < W; x += T) my[x] = g2[row + x];
+    __syncthreads();
+    if (!live) return;
+    for (int x = lx; x < W; x += T) {
+        const int own = my[x], s = own < 0 ? -1 : 1;
+        int best = own * s;                                   // the own column: the distance to the other set along it
+        const int reach = max(x, W - 1 - x);
+        for (int d = 1; d <= reach; ++d) {
+            const int dd = d * d;
+            if (dd >= best) break;
+            if (x - d >= 0) best = min(best, max(my[x - d] * s, 0) + dd);
+            if (x + d < W) best = min(best, max(my[x + d] * s, 0) + dd);
+        }
+        sd2[row + x] = best >= EDT_FAR ? 0 : best * s;
+    }
+}
+
+int signed_edt(const int64_t* target, int32_t* g2, int32_t* sd2, int N, int H, int W, int fg, int ignore, hipStream_t s) {
+    const int words = cdiv(H, 32), tiles = cdiv(W, EDT_SCOLS);
+    const unsigned cthreads = (unsigned)min(max(cdiv(words * EDT_SCOLS, 64) * 64, 64), MEDT_THREADS);
+    hipLaunchKernelGGL(signed_edt_cols_kernel, dim3((unsigned)N * tiles), dim3(cthreads), 0, s, target, g2, H, W, tiles, words,
+                       fg, ignore);
+    if (int rc = launch_status("signed_edt_cols")) return rc;
+    const int T = (int)edt_threads(W), rpb = W <= T ? MEDT_THREADS / T : 1, nrows = N * H;
+    hipLaunchKernelGGL(signed_edt_rows_kernel, dim3((unsigned)cdiv(nrows, rpb)), dim3((unsigned)(T * rpb)), 0, s, g2, sd2, W, T,
+                       rpb, nrows);
+    return launch_status("signed_edt_rows");
+}
+
+// --------------------------------------------------------------------------- //
+// Boundary term of the loss:  B = mean over images n of ( sum over valid p of phi_n(p) s_n(p) / max(1, V_n) ),
+//   s = softmax(logits)[fg],  phi = sqrt(sd2) outside F, -(sqrt(-sd2) - 1) inside (0 on the inner border), 0 where sd2 == 0
+//   (Kervadec's one_hot2dist), computed from the integers on the fly; valid: target in [0, K) and not `ignore`; V_n their count.
+// The grid of the segmentation loss above: a workgroup never straddles two images.  partials [N][bpi][2] = {sum phi s, V};
+// the finalize sums them in double in a fixed order and reads the weight alpha from device memory:
+//   out = [base + alpha B (alpha B when base is NULL), B, alpha, 1 / (N max(1, V_n)) for n < N]
+// The backward reads alpha and the last N floats again; with `accumulate` it adds into the dlogits the region loss's backward
+// wrote (one buffer, no second gradient tensor), else it writes, zeros at the pixels that are not valid included.
+// --------------------------------------------------------------------------- //
+__device__ __forceinline__ float boundary_phi(int sd2) {
+    if (sd2 > 0) return sqrtf((float)sd2);
+    if (sd2 < 0) return 1.f - sqrtf((float)-sd2);
+    return 0.f;
+}
+
+__global__ __launch_bounds__(MEDT_THREADS) void boundary_fwd_kernel(const float* __restrict__ logits,
+                                                                    const int64_t* __restrict__ target,
+                                                                    const int32_t* __restrict__ sd2,
+                                                                    float* __restrict__ partials, int K, int HW, int bpi,
+                                                                    int fg, int ignore) {
+    MEDT_STATIC_SHARED float red[MEDT_WAVES * 2];
+    const int n = blockIdx.x / bpi;
+    const int p = (blockIdx.x - n * bpi) * MEDT_THREADS + threadIdx.x;
+    float v[2] = {0.f, 0.f};
+    if (p < HW) {
+        const int64_t t = target[(size_t)n * HW + p];
+        if (t != ignore && t >= 0 && t < K) {
+            const float* lp = logits + (size_t)n * K * HW + p;
+            float m = lp[0];
+            for (int k = 1; k < K; ++k) m = fmaxf(m, lp[(size_t)k * HW]);
+            float sum = 0.f;
+            for (int k = 0; k < K; ++k) sum += __expf(lp[(size_t)k * HW] - m);
+            v[0] = boundary_phi(sd2[(size_t)n * HW + p]) * (__expf(lp[(size_t)fg * HW] - m) / sum);
+            v[1] = 1.f;
+        }
+    }
+    block_sum<2>(v, red, partials + (size_t)blockIdx.x * 2);
+}
+
+// One workgroup; wave w sums the partial rows of the images w, w + 4, .. in double, thread 0 adds the waves' totals in order.
+__global__ __launch_bounds__(MEDT_THREADS) void boundary_finalize_kernel(const float* __restrict__ partials,
+                                                                         const float* __restrict__ alpha,
+                                                                         const float* __restrict__ base,
+                                                                         float* __restrict__ out, int N, int bpi) {
+    MEDT_STATIC_SHARED double tot[MEDT_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double sb = 0.0;
+    for (int n = wave; n < N; n += MEDT_WAVES) {
+        double a = 0.0, c = 0.0;
+        for (int b = lane; b < bpi; b += 64) {
+            const float* pp = partials + ((size_t)n * bpi + b) * 2;
+            a += (double)pp[0];
+            c += (double)pp[1];
+        }
+        a = wave_sum_d(a);
+        c = wave_sum_d(c);
+        const double cnt = c > 1.0 ? c : 1.0;
+        sb += a / cnt;
+        if (lane == 0) out[3 + n] = (float)(1.0 / (cnt * (double)N));
+    }
+    if (lane == 0) tot[wave] = sb;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double B = 0.0;
+        for (int w = 0; w < MEDT_WAVES; ++w) B += tot[w];
+        B /= (double)N;
+        const float al = alpha[0];
+        const double term = (double)al * B;
+        out[0] = (float)(base ? (double)base[0] + term : term);
+        out[1] = (float)B;
+        out[2] = al;
+    }
+}
+
+// dlogits[n,k,p] (+)= dloss alpha phi / (N max(1, V_n)) * s (delta_k,fg - p_k)
+template <bool ACC>
+__global__ __launch_bounds__(MEDT_THREADS) void boundary_bwd_kernel(const float* __restrict__ logits,
+                                                                    const int64_t* __restrict__ target,
+                                                                    const int32_t* __restrict__ sd2,
+                                                                    const float* __restrict__ out,
+                                                                    const float* __restrict__ dloss,
+                                                                    float* __restrict__ dlogits, int K, int HW, int bpi, int fg,
+                                                                    int ignore) {
+    const int n = blockIdx.x / bpi;
+    const int p = (blockIdx.x - n * bpi) * MEDT_THREADS + threadIdx.x;
+    if (p >= HW) return;
+    const int64_t t = target[(size_t)n * HW + p];
+    const float* lp = logits + (size_t)n * K * HW + p;
+    float* dp = dlogits + (size_t)n * K * HW + p;
+    if (t == ignore || t < 0 || t >= K) {
+        if (!ACC)
+            for (int k = 0; k < K; ++k) dp[(size_t)k * HW] = 0.f;
+        return;                                               // ACC: the region loss's backward wrote the zeros
+    }
+    float m = lp[0];
+    for (int k = 1; k < K; ++k) m = fmaxf(m, lp[(size_t)k * HW]);
+    float sum = 0.f;
+    for (int k = 0; k < K; ++k) sum += __expf(lp[(size_t)k * HW] - m);
+    const float inv = 1.f / sum;
+    const float sf = __expf(lp[(size_t)fg * HW] - m) * inv;
+    const float c = (dloss ? dloss[0] : 1.f) * out[2] * out[3 + n] * boundary_phi(sd2[(size_t)n * HW + p]) * sf;
+    for (int k = 0; k < K; ++k) {
+        const float pk = __expf(lp[(size_t)k * HW] - m) * inv;
+        const float gk = c * ((k == fg ? 1.f : 0.f) - pk);
+        dp[(size_t)k * HW] = ACC ? dp[(size_t)k * HW] + gk : gk;
+    }
+}
+
+size_t boundary_partials(int N, int HW) { return (size_t)N * seg_loss_bpi(HW) * 2; }
+size_t boundary_out_floats(int N) { return 3 + (size_t)N; }
+
+int boundary_fwd(const float* logits, const int64_t* target, const int32_t* sd2, const float* alpha, const float* base,
+                 float* partials, float* out, int N, int K, int HW, int fg, int ignore, hipStream_t s) {
+    const int bpi = seg_loss_bpi(HW);
+    hipLaunchKernelGGL(boundary_fwd_kernel, dim3((unsigned)N * bpi), dim3(MEDT_THREADS), 0, s, logits, target, sd2, partials, K,
+                       HW, bpi, fg, ignore);
+    if (int rc = launch_status("boundary_fwd")) return rc;
+    hipLaunchKernelGGL(boundary_finalize_kernel, dim3(1), dim3(MEDT_THREADS), 0, s, partials, alpha, base, out, N, bpi);
+    return launch_status("boundary_finalize");
+}
+
+int boundary_bwd(const float* logits, const int64_t* target, const int32_t* sd2, const float* out, const float* dloss,
+                 float* dlogits, int N, int K, int HW, int fg, int ignore, int accumulate, hipStream_t s) {
+    const int bpi = seg_loss_bpi(HW);
+    const dim3 grid((unsigned)N * bpi), block(MEDT_THREADS);
+    if (accumulate)
+        hipLaunchKernelGGL(boundary_bwd_kernel<true>, grid, block, 0, s, logits, target, sd2, out, dloss, dlogits, K, HW, bpi, fg,
+                           ignore);
+    else
+        hipLaunchKernelGGL(boundary_bwd_kernel<false>, grid, block, 0, s, logits, target, sd2, out, dloss, dlogits, K, HW, bpi,
+                           fg, ignore);
+    return launch_status("boundary_bwd");
+}
+
 }  // namespace medt

@@ -1037,6 +1037,45 @@ int medt_edt_rows(const int32_t* g2, const uint8_t* select, int32_t* d2, int N, 
     return edt_rows(g2, select, d2, N, H, W, (hipStream_t)stream);
 }
 
+int medt_signed_edt(const int64_t* target, int32_t* g2, int32_t* sd2, int N, int H, int W, int fg, int ignore_index, void* stream) {
+    if (const int rc = edt_geometry("signed_edt", N, H, W)) return rc;
+    if (!target || !g2 || !sd2 || g2 == sd2) { set_error("signed_edt: null target, g2 or sd2, or sd2 is g2"); return MEDT_EINVAL; }
+    if (fg < 0) { set_error("signed_edt: foreground class %d: a class index >= 0 expected", fg); return MEDT_EINVAL; }
+    return signed_edt(target, g2, sd2, N, H, W, fg, ignore_index, (hipStream_t)stream);
+}
+
+// sizes and the foreground class of medt_boundary_*
+static int boundary_args(const char* what, int N, int K, int HW, int fg) {
+    if (N < 1 || K < 2 || HW < 1) {
+        set_error("%s: bad arguments (N %d, K %d, HW %d; two classes or more)", what, N, K, HW); return MEDT_EINVAL;
+    }
+    if (fg < 0 || fg >= K) { set_error("%s: foreground class %d outside [0, %d)", what, fg, K); return MEDT_EINVAL; }
+    if ((double)N * seg_loss_bpi(HW) >= 2147483648.0 || (double)N * HW >= 2147483648.0) {
+        set_error("%s: %d images of %d pixels: too large a grid", what, N, HW); return MEDT_EUNSUPPORTED;
+    }
+    return MEDT_OK;
+}
+size_t medt_boundary_workspace(int N, int HW) {
+    if (boundary_args("boundary workspace", N, 2, HW, 0)) return 0;
+    return boundary_partials(N, HW);
+}
+size_t medt_boundary_out_floats(int N) {
+    if (boundary_args("boundary out_floats", N, 2, 1, 0)) return 0;
+    return boundary_out_floats(N);
+}
+int medt_boundary_fwd(const float* logits, const int64_t* target, const int32_t* sd2, const float* alpha, const float* base,
+                      float* partials, float* out, int N, int K, int HW, int fg, int ignore_index, void* stream) {
+    if (!logits || !target || !sd2 || !alpha || !partials || !out) { set_error("boundary fwd: null pointer"); return MEDT_EINVAL; }
+    if (int rc = boundary_args("boundary fwd", N, K, HW, fg)) return rc;
+    return boundary_fwd(logits, target, sd2, alpha, base, partials, out, N, K, HW, fg, ignore_index, (hipStream_t)stream);
+}
+int medt_boundary_bwd(const float* logits, const int64_t* target, const int32_t* sd2, const float* out, const float* dloss,
+                      float* dlogits, int N, int K, int HW, int fg, int ignore_index, int accumulate, void* stream) {
+    if (!logits || !target || !sd2 || !out || !dlogits) { set_error("boundary bwd: null pointer"); return MEDT_EINVAL; }
+    if (int rc = boundary_args("boundary bwd", N, K, HW, fg)) return rc;
+    return boundary_bwd(logits, target, sd2, out, dloss, dlogits, N, K, HW, fg, ignore_index, accumulate, (hipStream_t)stream);
+}
+
 static int label_geometry(const char* what, int N, int H, int W) {
     if (N < 1 || H < 1 || W < 1) {
         set_error("%s: bad arguments (%d images of %d x %d)", what, N, H, W); return MEDT_EINVAL;

@@ -132,6 +132,14 @@ int augment_apply(const uint8_t* image, const uint8_t* mask, const float* params
 // exact squared Euclidean distance transform in two passes (medt_abi.h): columns (of the mask, or of its border), then rows
 int edt_cols(const uint8_t* mask, int32_t* g2, int N, int H, int W, int border_mode, hipStream_t s);
 int edt_rows(const int32_t* g2, const uint8_t* select, int32_t* d2, int N, int H, int W, hipStream_t s);
+// signed squared distance map of {target == fg} (two launches) and the boundary term of the loss on it (medt_abi.h)
+int signed_edt(const int64_t* target, int32_t* g2, int32_t* sd2, int N, int H, int W, int fg, int ignore, hipStream_t s);
+size_t boundary_partials(int N, int HW);
+size_t boundary_out_floats(int N);
+int boundary_fwd(const float* logits, const int64_t* target, const int32_t* sd2, const float* alpha, const float* base,
+                 float* partials, float* out, int N, int K, int HW, int fg, int ignore, hipStream_t s);
+int boundary_bwd(const float* logits, const int64_t* target, const int32_t* sd2, const float* out, const float* dloss,
+                 float* dlogits, int N, int K, int HW, int fg, int ignore, int accumulate, hipStream_t s);
 // connected-component labelling, component tables, table-driven select (label.hip; medt_abi.h)
 size_t label_workspace_bytes(int N, int H, int W);
 int label_components(const uint8_t* mask, int32_t* labels, int32_t* count, void* workspace, int N, int H, int W, int connectivity,

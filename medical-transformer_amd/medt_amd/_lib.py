@@ -157,6 +157,11 @@ SIGNATURES = {
     "medt_augment_apply": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p]),
     "medt_edt_cols": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "medt_edt_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
+    "medt_signed_edt": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "medt_boundary_workspace": (C.c_size_t, [C.c_int, C.c_int]),
+    "medt_boundary_out_floats": (C.c_size_t, [C.c_int]),
+    "medt_boundary_fwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p]),
+    "medt_boundary_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p]),
     "medt_label_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "medt_label_components": (C.c_int, [C.c_void_p] * 4 + [C.c_size_t] + [C.c_int] * 5 + [C.c_void_p]),
     "medt_label_tables": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),

@@ -486,6 +486,130 @@ def seg_loss(logits, target, weight=None, ce=1.0, dice=0.0, eps=1.0, ignore_inde
 
 
 # --------------------------------------------------------------------------- #
+# boundary loss (Kervadec et al., MIDL 2019) on the signed distance map of the step's own label map
+# --------------------------------------------------------------------------- #
+class SegBoundaryFn(torch.autograd.Function):
+    """region loss (medt_seg_loss_*, unchanged; left out when ce == dice == 0) + alpha * boundary term as ONE node: the
+    boundary finalize adds the region loss on the device, the boundary backward adds into the region backward's dlogits."""
+
+    @staticmethod
+    def forward(ctx, logits, target, alpha, weight, ce, dice, eps, fg, ignore_index):
+        _require_device(logits)
+        lib = L.lib()
+        logits, target = logits.contiguous(), target.contiguous()
+        N, K = logits.shape[0], logits.shape[1]
+        HW = logits[0, 0].numel()
+        region = ce != 0.0 or dice != 0.0
+        rout = None
+        if region:
+            nws, nout = lib.medt_seg_loss_workspace(N, K, HW), lib.medt_seg_loss_out_floats(N, K)
+            if not nws or not nout:
+                raise L.MedtError(f"seg_boundary_loss: {lib.medt_last_error().decode()}")
+            partials = torch.empty((nws,), device=logits.device, dtype=torch.float32)
+            rout = torch.empty((nout,), device=logits.device, dtype=torch.float32)
+            L.check(lib.medt_seg_loss_fwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), partials.data_ptr(), rout.data_ptr(),
+                                          N, K, HW, ignore_index, ce, dice, eps, _stream()), "medt_seg_loss_fwd")
+        sd2 = signed_edt_sq(target, fg, ignore_index)
+        nws, nout = lib.medt_boundary_workspace(N, HW), lib.medt_boundary_out_floats(N)
+        if not nws or not nout:
+            raise L.MedtError(f"boundary_loss: {lib.medt_last_error().decode()}")
+        bparts = torch.empty((nws,), device=logits.device, dtype=torch.float32)
+        bout = torch.empty((nout,), device=logits.device, dtype=torch.float32)
+        L.check(lib.medt_boundary_fwd(logits.data_ptr(), target.data_ptr(), sd2.data_ptr(), alpha.data_ptr(), L.ptr(rout),
+                                      bparts.data_ptr(), bout.data_ptr(), N, K, HW, fg, ignore_index, _stream()),
+                "medt_boundary_fwd")
+        saved = [logits, target, sd2, bout] + ([rout] if region else []) + ([weight] if weight is not None else [])
+        ctx.save_for_backward(*saved)
+        ctx.cfg = (ce, dice, eps, fg, ignore_index, region, weight is not None)
+        loss = bout[0]
+        outs = (bout, rout) if region else (bout,)
+        ctx.mark_non_differentiable(*outs)
+        ctx.set_materialize_grads(False)
+        return (loss,) + outs
+
+    @staticmethod
+    def backward(ctx, dloss, *_):
+        if dloss is None:
+            return (None,) * 9
+        lib = L.lib()
+        ce, dice, eps, fg, ignore_index, region, weighted = ctx.cfg
+        logits, target, sd2, bout, *rest = ctx.saved_tensors
+        rout = rest.pop(0) if region else None
+        weight = rest.pop(0) if weighted else None
+        N, K = logits.shape[0], logits.shape[1]
+        HW = logits[0, 0].numel()
+        dloss = dloss.contiguous().float()
+        dlogits = torch.empty_like(logits)
+        if region:
+            L.check(lib.medt_seg_loss_bwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), rout.data_ptr(), dloss.data_ptr(),
+                                          dlogits.data_ptr(), N, K, HW, ignore_index, ce, dice, eps, _stream()),
+                    "medt_seg_loss_bwd")
+        L.check(lib.medt_boundary_bwd(logits.data_ptr(), target.data_ptr(), sd2.data_ptr(), bout.data_ptr(), dloss.data_ptr(),
+                                      dlogits.data_ptr(), N, K, HW, fg, ignore_index, int(region), _stream()),
+                "medt_boundary_bwd")
+        return (dlogits,) + (None,) * 8
+
+
+def _boundary_args(what, logits, target, alpha, fg):
+    if logits.dim() != 4 or logits.dtype != torch.float32:
+        raise L.MedtError(f"{what}: float32 (N,K,H,W) logits expected")
+    if (target.dtype != torch.int64 or target.device != logits.device or target.dim() != 3
+            or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:])):
+        raise L.MedtError(f"{what}: int64 (N,H,W) class-index targets on the logits' device expected")
+    K = logits.shape[1]
+    if K < 2 or not 0 <= int(fg) < K:
+        raise L.MedtError(f"{what}: two classes or more and a foreground class in [0, K) expected (K = {K}, fg = {fg})")
+    if torch.is_tensor(alpha):
+        if alpha.dtype != torch.float32 or alpha.numel() != 1 or alpha.device != logits.device:
+            raise L.MedtError(f"{what}: alpha must be one float32 on the logits' device (or a number)")
+        return alpha.detach()
+    return torch.full((1,), float(alpha), device=logits.device, dtype=torch.float32)
+
+
+def boundary_loss(logits, target, alpha, fg=1, ignore_index=-100):
+    """alpha * B, the boundary term alone, of (N,K,H,W) float32 logits against (N,H,W) int64 class indices:
+    B = mean over images n of ( sum over the valid pixels p of phi_n(p) * softmax(logits)[n,fg,p] / max(1, V_n) ),
+    phi = sqrt(sd2) outside F = {target == fg}, -(sqrt(-sd2) - 1) inside (0 on the inner border), sd2 = signed_edt_sq(target, fg)
+    (Kervadec's one_hot2dist, computed on the device from the step's own label map, never stored as floats).  A pixel is valid
+    when its target is in [0, K) and not `ignore_index`; the others contribute nothing and receive gradient exactly 0.  Per
+    image, not per batch, for seg_loss's reason (equal shards under data parallel).  alpha: a one-element float32 device tensor,
+    READ ON THE DEVICE by the kernels (refill it in place and a captured step follows), or a number.  Two launches for the map,
+    two forward, one backward; no float atomics.  loss._medt_boundary_out = [alpha B, B, alpha, ...]."""
+    alpha = _boundary_args("boundary_loss", logits, target, alpha, fg)
+    loss, bout = SegBoundaryFn.apply(logits, target, alpha, None, 0.0, 0.0, 1.0, int(fg), int(ignore_index))
+    loss._medt_boundary_out = bout
+    return loss
+
+
+def seg_boundary_loss(logits, target, alpha, weight=None, ce=1.0, dice=0.0, eps=1.0, fg=1, ignore_index=-100):
+    """seg_loss(logits, target, weight, ce, dice, eps, ignore_index) + alpha * B with B of boundary_loss(), as one
+    autograd node: the region term runs through the unchanged medt_seg_loss_* entry points, the boundary finalize adds it on the
+    device and the boundary backward adds into the dlogits the region backward has just written -- one gradient buffer, no torch
+    add.  With alpha == 0 loss and gradient are seg_loss's, bit for bit.  loss._medt_ce_out is the region term's `out` (so
+    TrainStep.check_targets() works as with seg_loss), loss._medt_boundary_out = [loss, B, alpha, ...]."""
+    alpha = _boundary_args("seg_boundary_loss", logits, target, alpha, fg)
+    K = logits.shape[1]
+    if weight is not None:
+        if (not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.dim() != 1 or weight.numel() != K
+                or weight.device != logits.device):
+            raise L.MedtError(f"seg_boundary_loss: weight must be a float32 tensor of {K} class weights on the logits' device")
+        weight = weight.detach().contiguous()
+    ce, dice, eps = float(ce), float(dice), float(eps)
+    if ce == 0.0 and dice == 0.0:
+        raise L.MedtError("seg_boundary_loss: no region term (ce == dice == 0): boundary_loss() is the term alone")
+    if dice != 0.0 and not 2 <= K <= 8:
+        raise L.MedtError(f"seg_boundary_loss: soft Dice needs 2 <= K <= 8 classes (K = {K})")
+    if not eps >= 0.0:
+        raise L.MedtError("seg_boundary_loss: eps >= 0 expected")
+    loss, bout, rout = SegBoundaryFn.apply(logits, target, alpha, weight, ce, dice, eps, int(fg), int(ignore_index))
+    loss._medt_ce_out = rout
+    loss._medt_boundary_out = bout
+    if CHECK_TARGETS and not torch.cuda.is_current_stream_capturing():
+        raise_on_bad_targets(rout, K)
+    return loss
+
+
+# --------------------------------------------------------------------------- #
 # segmentation scoring (replaces performancemetrics_*.m)
 # --------------------------------------------------------------------------- #
 def seg_counts(logits, target, threshold=0.5):
@@ -672,6 +796,30 @@ def surface_d2(a, b, out=None):
     L.check(lib.medt_edt_cols(mb.data_ptr(), g2.data_ptr(), N, H, W, 1, _stream()), "medt_edt_cols")
     L.check(lib.medt_edt_rows(g2.data_ptr(), ma.data_ptr(), d2.data_ptr(), N, H, W, _stream()), "medt_edt_rows")
     return d2
+
+
+def signed_edt_sq(target, fg=1, ignore_index=-100, out=None):
+    """int64 (N,H,W) or (H,W) class indices -> int32 of the same shape: the signed squared Euclidean distance to the boundary of
+    F = {target == fg}: +d^2 to the nearest pixel of F at a pixel outside F (>= 1), -d^2 to the nearest pixel outside F at a
+    pixel of F (<= -1).  Ignored pixels, other classes and class indices out of range are all outside F.  An image without F
+    holds 0 everywhere, and so does an image that is all F (SciPy's value for an input without a zero is arbitrary).  Exact and
+    bit-identical from run to run; at most 4096 pixels per side.  out: a contiguous int32 tensor to write into (any alignment:
+    the kernels use element accesses).  The label map of the training step as it stands: no uint8 copy is made."""
+    _require_device(target.new_empty(0, dtype=torch.float32))      # (the device check; the label map itself is int64)
+    if target.dtype != torch.int64 or target.dim() not in (2, 3):
+        raise L.MedtError("signed_edt_sq: an int64 (N,H,W) or (H,W) map of class indices expected")
+    if target.numel() == 0:
+        raise L.MedtError("signed_edt_sq: empty label map")
+    fg, ignore_index = int(fg), int(ignore_index)
+    if fg < 0:
+        raise L.MedtError(f"signed_edt_sq: foreground class {fg}: a class index >= 0 expected")
+    t = target.contiguous().reshape(-1, *target.shape[-2:])
+    N, H, W = t.shape
+    sd2 = _edt_out("signed_edt_sq", out, target)
+    g2 = torch.empty(t.shape, device=t.device, dtype=torch.int32)
+    L.check(L.lib().medt_signed_edt(t.data_ptr(), g2.data_ptr(), sd2.data_ptr(), N, H, W, fg, ignore_index, _stream()),
+            "medt_signed_edt")
+    return sd2
 
 
 # --------------------------------------------------------------------------- #

@@ -43,6 +43,30 @@ class DiceCELoss(torch.nn.Module):
                                  ignore_index=self.ignore_index)
 
 
+class BoundaryLoss(torch.nn.Module):
+    """ce * (class-weighted) cross entropy + dice * soft Dice + alpha * boundary loss (Kervadec et al., MIDL 2019) of the
+    class `fg`: medt_amd.seg_boundary_loss has the formulas.  The signed distance map comes from the label map the step holds
+    on the device (after the device-side augmentation, where there is one), not from the dataset.
+
+    `alpha` is a registered float32 buffer of one element that the kernels read on the device: set_alpha() fills it in place,
+    so a captured step follows the schedule without another capture."""
+
+    def __init__(self, alpha=0.01, weight=None, ce=1.0, dice=0.0, eps=1.0, fg=1, ignore_index=-100):
+        super().__init__()
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32).reshape(-1)
+        self.register_buffer("weight", weight)
+        self.register_buffer("alpha", torch.full((1,), float(alpha), dtype=torch.float32))
+        self.ce, self.dice, self.eps, self.fg, self.ignore_index = float(ce), float(dice), float(eps), int(fg), ignore_index
+
+    def set_alpha(self, v):
+        self.alpha.fill_(float(v))
+
+    def forward(self, y_input, y_target):
+        return medt_amd.seg_boundary_loss(y_input, y_target, self.alpha, weight=self.weight, ce=self.ce, dice=self.dice,
+                                          eps=self.eps, fg=self.fg, ignore_index=self.ignore_index)
+
+
 def classwise_iou(output, gt):
     dims = (0, *range(2, len(output.shape)))
     onehot = torch.zeros_like(output).scatter_(1, gt[:, None, :], 1)

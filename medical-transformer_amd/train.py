@@ -13,6 +13,9 @@ Differences, all host-side plumbing:
   * --synthetic N writes N synthetic PNG pairs into --train_dataset first (BASELINE.json config 1 plumbing);
   * --loss {ce,dice,ce+dice} and --class_weights "w0,w1" pick the criterion (metrics.DiceCELoss / LogNLLLoss(weight)); the
     defaults are the reference's LogNLLLoss();
+  * --loss ce+boundary / dice+boundary / ce+dice+boundary add the boundary loss of Kervadec et al. (metrics.BoundaryLoss; the
+    signed distance map is computed on the GPU from the batch's own masks); its weight starts at --boundary_alpha, grows by
+    --boundary_step after every epoch up to --boundary_max, and is printed as `boundary alpha` before the epoch line;
   * --aug on moves the joint transform to the GPU (medt_amd.augment: the uint8 image is uploaded, two kernels crop, flip,
     jitter and map it); --aug_jitter "b,c,s,h" and --aug_affine P add the colour jitter and the random affine map the
     reference's JointTransform2D has and its train.py never enables; --aug off (the default) is the host transform as before;
@@ -27,7 +30,7 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 
 import lib
-from metrics import DiceCELoss, LogNLLLoss
+from metrics import BoundaryLoss, DiceCELoss, LogNLLLoss
 from medt_amd import dp
 from medt_amd.data import DevicePrefetcher, imwrite, make_synthetic_dataset
 from medt_amd.optim import FlatAdam
@@ -58,14 +61,37 @@ parser.add_argument('--device', default='cuda', type=str)
 parser.add_argument('--gray', default='no', type=str)
 parser.add_argument('--synthetic', type=int, default=0, help='write this many synthetic PNG pairs into the dataset dirs first')
 parser.add_argument('--eager', action='store_true', help='no hipGraph replay')
-parser.add_argument('--loss', default='ce', choices=['ce', 'dice', 'ce+dice'], help='cross entropy, soft Dice or their sum (default: ce)')
+parser.add_argument('--loss', default='ce', choices=['ce', 'dice', 'ce+dice', 'ce+boundary', 'dice+boundary', 'ce+dice+boundary'],
+                    help='cross entropy, soft Dice or their sum, +boundary: plus the boundary loss (default: ce)')
 parser.add_argument('--class_weights', default=None, type=str, help='comma-separated class weights of the cross entropy, e.g. "1,3"')
+parser.add_argument('--boundary_alpha', default=None, type=float, help='with a +boundary loss: weight of the boundary term in the first epoch (default: 0.01)')
+parser.add_argument('--boundary_step', default=None, type=float, help='with a +boundary loss: added to the weight after every epoch (default: 0.01)')
+parser.add_argument('--boundary_max', default=None, type=float, help='with a +boundary loss: the weight stops growing here (default: 1.0)')
 
 NUM_CLASSES = 2          # every network of lib.models ends in a 2-channel adjust convolution
 
 
-def make_criterion(loss, class_weights):
+def make_boundary(loss, alpha, step, vmax):
+    """None without a +boundary loss, else the schedule of the boundary term's weight: alpha in the first epoch, + step after
+    every epoch, at most max."""
+    if not loss.endswith("+boundary"):
+        if alpha is not None or step is not None or vmax is not None:
+            raise SystemExit("--boundary_alpha / --boundary_step / --boundary_max belong to the boundary loss: "
+                             "use --loss ce+boundary, dice+boundary or ce+dice+boundary")
+        return None
+    sched = {"alpha": 0.01 if alpha is None else alpha, "step": 0.01 if step is None else step, "max": 1.0 if vmax is None else vmax}
+    if not (sched["alpha"] >= 0.0 and sched["step"] >= 0.0 and sched["max"] >= sched["alpha"]):
+        raise SystemExit("--boundary_alpha, --boundary_step >= 0 and --boundary_max >= --boundary_alpha expected, got %r" % (sched,))
+    return sched
+
+
+def boundary_alpha(sched, epoch):
+    return min(sched["max"], sched["alpha"] + sched["step"] * epoch)
+
+
+def make_criterion(loss, class_weights, boundary=None):
     weight = None
+    region = loss[:-len("+boundary")] if loss.endswith("+boundary") else loss
     if class_weights is not None:
         try:
             weight = [float(w) for w in class_weights.split(",")]
@@ -73,9 +99,12 @@ def make_criterion(loss, class_weights):
             raise SystemExit("--class_weights: comma-separated numbers expected, got %r" % class_weights)
         if len(weight) != NUM_CLASSES:
             raise SystemExit("--class_weights: %d weights given, the networks have %d classes" % (len(weight), NUM_CLASSES))
-        if loss == "dice":
+        if region == "dice":
             raise SystemExit("--class_weights weigh the cross entropy: use --loss ce or ce+dice")
         weight = torch.tensor(weight, dtype=torch.float32)
+    if region != loss:
+        return BoundaryLoss(alpha=0.01 if boundary is None else boundary["alpha"], weight=weight, ce=0.0 if region == "dice" else 1.0,
+                            dice=0.0 if region == "ce" else 1.0)
     if loss == "ce":
         return LogNLLLoss() if weight is None else LogNLLLoss(weight=weight)         # the defaults: reference train.py:110
     return DiceCELoss(weight=weight, ce=0.0 if loss == "dice" else 1.0, dice=1.0)
@@ -103,7 +132,8 @@ def make_augment(aug, aug_jitter, aug_affine):
 
 def main():
     args = parser.parse_args()
-    criterion = make_criterion(args.loss, args.class_weights)      # (a bad --class_weights ends the run before any work)
+    boundary = make_boundary(args.loss, args.boundary_alpha, args.boundary_step, args.boundary_max)    # (so do --boundary_* alone)
+    criterion = make_criterion(args.loss, args.class_weights, boundary)      # (a bad --class_weights ends the run before any work)
     augment = make_augment(args.aug, args.aug_jitter, args.aug_affine)              # (so does a bad --aug_* combination)
     direc, modelname, imgsize = args.direc, args.modelname, args.imgsize
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -175,6 +205,8 @@ def main():
         if sampler is not None:
             sampler.set_epoch(epoch)
         epoch_running_loss, batch_idx = 0.0, -1
+        if boundary is not None:                  # filled in place: the captured step reads the weight from device memory
+            criterion.set_alpha(boundary_alpha(boundary, epoch))
         # host decode + pinned staging + H2D run one step ahead on a copy stream (reference: blocking .to(), :134-135)
         for batch_idx, (X_batch, y_batch, *rest) in enumerate(DevicePrefetcher(dataloader, device, stage=3 if device_aug else 2)):
             X_batch = X_batch.to(device)
@@ -184,6 +216,8 @@ def main():
             loss = train_step(X_batch, y_batch)
             epoch_running_loss += loss.item()
             train_step.check_targets()            # mislabelled masks raise, as F.cross_entropy does in the reference
+        if rank == 0 and boundary is not None:
+            print('boundary alpha {:.4f}'.format(boundary_alpha(boundary, epoch)))
         if rank == 0:
             print('epoch [{}/{}], loss:{:.4f}'.format(epoch, args.epochs, epoch_running_loss / (batch_idx + 1)))
 

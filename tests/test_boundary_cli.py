@@ -1,0 +1,79 @@
+"""train.py --loss ce+dice+boundary (after tests/test_seg_loss_cli.py): three epochs of gatedaxialunet on synthetic images with
+the boundary weight growing by 0.05 per epoch, replayed and eager -- the same loss lines, the `boundary alpha` lines of the
+schedule -- and the refusal of the --boundary_* flags without a +boundary loss."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+import helpers as H  # noqa: F401
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "medical-transformer_amd")
+
+
+def run_train(tmp_path, tag, emulating, extra):
+    env = dict(os.environ, PYTHONPATH=PKG)
+    d, out = str(tmp_path / "data"), str(tmp_path / ("run_" + tag))
+    # train.py itself, behind one torch.manual_seed(): it builds the model before it seeds anything, so without the driver two
+    # processes start from different weights and no two runs print the same losses (tests/boundary_cli_driver.py)
+    driver = [sys.executable, os.path.join(ROOT, "tests", "boundary_cli_driver.py")]
+    if emulating:
+        cmd = driver + ["--emulated", "--imgsize", "32", "--synthetic", "2", "--device", "cpu"]
+    else:
+        cmd = driver + ["--imgsize", "64", "--synthetic", "6"]
+    r = subprocess.run(cmd + ["--batch_size", "2", "--save_freq", "10", "--train_dataset", d, "--val_dataset", d, "--direc", out,
+                              "--epochs", "3", "--modelname", "gatedaxialunet", "--learning_rate", "0.001", "--gray", "no", "--loss",
+                              "ce+dice+boundary", "--boundary_step", "0.05"] + extra,
+                       env=env, capture_output=True, text=True, timeout=3000 if emulating else 600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return r.stdout
+
+
+@pytest.mark.gpu
+def test_train_cli_boundary_schedule_replayed_equals_eager(tmp_path, device, emulating):
+    """On the GPU: 6 images of 64 px in batches of 2, replayed and --eager: identical loss lines.  Under --emulate: train.py on the
+    emulated device (tests/boundary_cli_driver.py --emulated), which has no graphs: the eager run alone, 2 images of 32 px.
+
+    KNOWN TO FAIL on the MI355X in its last assertion, the equality of the loss lines; everything before it holds (the six lines
+    in order, the alpha lines 0.0100 / 0.0600 / 0.1100, finite losses).  Measured, same weights and data in both runs: eager
+    1.2092 / 1.2099 / 1.2206, replayed 1.2092 / 1.2097 / 1.2205 (another box: 1.2158 / .. / 1.2209 against 1.2157 / .. / 1.2208).
+    Either mode repeats itself exactly from run to run.  The gap is not the boundary loss's: the same two commands with
+    `--loss ce+dice`, code this feature does not touch, print 1.2070 / 1.1952 / 1.1933 eager against 1.2069 / 1.1950 / 1.1934
+    replayed, and TrainStep with BoundaryLoss IS bit-identical between eager and replayed steps when both start alike
+    (tests/test_boundary_gpu.py::test_train_step_follows_alpha_without_recapture).  What differs, as far as the code shows
+    (supposed, not isolated by an experiment): train.py --eager spends its first step adopting the parameters into FlatAdam's flat
+    buffers with the gradients arriving through autograd, while the replayed run does that in warm-up steps it rolls back before
+    capture -- the difference the step tests remove by giving the eager run a rolled-back warm-up by hand; rounding-level
+    differences of the first update then grow through training-mode BatchNorm.  Making the two modes of train.py agree means
+    changing what --eager does today, which is outside this feature."""
+    eager = run_train(tmp_path, "eager", emulating, ["--eager"])
+    lines = re.findall(r"^(?:boundary alpha|epoch \[).*$", eager, flags=re.M)
+    assert len(lines) == 6 and [l.startswith("boundary alpha") for l in lines] == [True, False] * 3, eager
+    assert re.findall(r"^boundary alpha ([0-9.]+)$", eager, flags=re.M) == ["0.0100", "0.0600", "0.1100"]
+    losses = [float(v) for v in re.findall(r"epoch \[\d+/3\], loss:([0-9.naninf-]+)", eager)]
+    assert len(losses) == 3 and all(-100.0 < v < 100.0 for v in losses), eager           # finite (nan fails every comparison)
+    if emulating:
+        return
+    replayed = run_train(tmp_path, "replayed", emulating, [])
+    assert re.findall(r"^(?:boundary alpha|epoch \[).*$", replayed, flags=re.M) == lines
+
+
+def test_boundary_flags_without_a_boundary_loss_end_the_run(tmp_path):
+    """A clear message, before any work (no GPU, no dataset needed); and the three new choices of --loss parse."""
+    env = dict(os.environ, PYTHONPATH=PKG)
+    for flag in ("--boundary_alpha", "--boundary_step", "--boundary_max"):
+        r = subprocess.run([sys.executable, os.path.join(PKG, "train.py"), "--train_dataset", str(tmp_path / "none"), "--loss",
+                            "ce+dice", flag, "0.1"], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and "belong to the boundary loss" in r.stderr, r.stderr[-500:]
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("cli_train_boundary_flags", os.path.join(PKG, "train.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    for loss in ("ce+boundary", "dice+boundary", "ce+dice+boundary"):
+        a = mod.parser.parse_args(["--train_dataset", "x", "--loss", loss, "--boundary_alpha", "0.2", "--boundary_max", "0.3"])
+        sched = mod.make_boundary(a.loss, a.boundary_alpha, a.boundary_step, a.boundary_max)
+        assert sched == {"alpha": 0.2, "step": 0.01, "max": 0.3}
+        assert [round(mod.boundary_alpha(sched, e), 6) for e in range(12)][-2:] == [0.3, 0.3]
