@@ -40,7 +40,8 @@ extern "C" {
  * so a caller built against the earlier header keeps working.  The medt_label_* entry points were added under the same
  * number: additions only, nothing that version 11 declared was removed or changed, so a caller built against the earlier
  * header keeps working.  medt_label_boxes and medt_pair_hausdorff were added under the same number, in the same way.
- * medt_signed_edt and the medt_boundary_* entry points were added under the same number, in the same way. */
+ * medt_signed_edt and the medt_boundary_* entry points were added under the same number, in the same way.  medt_object_edt2
+ * and the medt_border_* entry points were added under the same number, in the same way. */
 #define MEDT_ABI_VERSION 11
 
 #define MEDT_OK            0
@@ -490,6 +491,45 @@ int medt_boundary_fwd(const float* logits, const int64_t* target, const int32_t*
                       float* partials, float* out, int N, int K, int HW, int fg, int ignore_index, void* stream);
 int medt_boundary_bwd(const float* logits, const int64_t* target, const int32_t* sd2, const float* out, const float* dloss,
                       float* dlogits, int N, int K, int HW, int fg, int ignore_index, int accumulate, void* stream);
+
+/* Border weight of the training step for touching objects (Ronneberger et al., "U-Net", MICCAI 2015: w0 exp(-(d1 + d2)^2 /
+ * (2 sigma^2)), d1 and d2 the distances to the nearest and the second-nearest object), as an additive term of the loss.
+ *
+ * medt_object_edt2: labels (N,H,W) int32 as medt_label_components writes them (0: no object, l > 0: object l; values <= 0 are
+ * no object) -> d1sq, d2sq (N,H,W) int32, in two launches (columns, rows).  d1sq: the squared distance to the nearest pixel
+ * with a label > 0 (0 inside an object).  d2sq: the squared distance to the nearest pixel with a label > 0 other than the label
+ * that attains d1sq -- the second smallest of the per-object minimum distances; inside object l the distance to the nearest
+ * other object.  MEDT_EDT_NONE where there is no such object: d1sq in an image without an object, d2sq in an image with fewer
+ * than two.  Labels are not returned: under ties the nearest label is not unique, the two distances are.
+ * scratch: 4 * N*H*W int32, four planes of N*H*W each: g1 | a | g2 | b -- per pixel the squared distance along its column to
+ * the nearest labelled pixel of the column and that pixel's label, then the same for the nearest pixel of the column whose
+ * label is not a (2^30 and label 0 where the column has none); must not alias d1sq or d2sq, which must differ.  Exact: integers
+ * throughout, no atomics, no workgroup waits for another, bit-identical from run to run.  Element accesses only: no alignment
+ * beyond the elements' own.  Limits as medt_edt_*: 1 <= H, W <= MEDT_EDT_MAX_DIM, N*H*W below 2^31 (MEDT_EUNSUPPORTED beyond,
+ * before any launch).
+ *
+ * medt_border_fwd / _bwd: logits (N,K,HW) float32, target (N,HW) int64, d1sq / d2sq (N,HW) from medt_object_edt2 over the
+ * components of F = {target == fg}; K >= 2, 0 <= fg < K, sigma > 0 and finite (MEDT_EINVAL otherwise).
+ *   e = exp(-(sqrt(d1sq) + sqrt(d2sq))^2 / (2 sigma^2)) at the pixels whose target is not fg and whose d2sq is not
+ *   MEDT_EDT_NONE, 0 elsewhere (computed on the fly, never stored);  nll = -log softmax(logits)[target];
+ *   R = mean over images n of ( sum over the valid pixels p of e_n(p) nll_n(p) / max(1, V_n) ), valid and V_n as medt_boundary_fwd.
+ * w0: ONE float32 in device memory, read on the device and handed on in out[2], as medt_boundary_fwd's alpha.  base: NULL, or
+ * one device float (the region loss).
+ *   out: medt_border_out_floats(N) floats = [base + w0 R (w0 R when base is NULL), R, w0 as read, 1 / (N max(1, V_n)) for n < N];
+ *   partials: medt_border_workspace(N, HW) floats.  fwd is two launches (partial sums, one finalize in double), bwd one; every
+ *   sum has a fixed order, no float atomics.
+ *   bwd: dlogits[n,k,p] = dloss w0 e / (N max(1, V_n)) (p_k - delta(k, target)) at the valid pixels (dloss: one device float,
+ *   NULL = 1).  accumulate == 0 writes dlogits, zeros where e is 0 included; accumulate != 0 ADDS into the dlogits that
+ *   medt_seg_loss_bwd / medt_ce_bwd has just written for the same logits and targets. */
+int medt_object_edt2(const int32_t* labels, int32_t* scratch, int32_t* d1sq, int32_t* d2sq, int N, int H, int W, void* stream);
+size_t medt_border_workspace(int N, int HW);
+size_t medt_border_out_floats(int N);
+int medt_border_fwd(const float* logits, const int64_t* target, const int32_t* d1sq, const int32_t* d2sq, float sigma,
+                    const float* w0, const float* base, float* partials, float* out, int N, int K, int HW, int fg,
+                    int ignore_index, void* stream);
+int medt_border_bwd(const float* logits, const int64_t* target, const int32_t* d1sq, const int32_t* d2sq, float sigma,
+                    const float* out, const float* dloss, float* dlogits, int N, int K, int HW, int fg, int ignore_index,
+                    int accumulate, void* stream);
 
 /* Connected-component labelling of binary masks on the device, the per-component tables and a table-driven select pass -- the
  * building blocks of the object-level scores (metrics.object_scores: GlaS object F1 / Dice, AJI, PQ) and of the two mask

@@ -1856,4 +1856,293 @@ int boundary_bwd(const float* logits, const int64_t* target, const int32_t* sd2,
     return launch_status("boundary_bwd");
 }
 
+// --------------------------------------------------------------------------- //
+// Two-nearest-object distance transform of a label map (0 = no object, l > 0 = object l; label.hip writes such maps), for the
+// border weight of the training step (Ronneberger et al., U-Net, 2015):
+//   d1sq = squared distance to the nearest labelled pixel, d2sq = squared distance to the nearest labelled pixel of ANOTHER
+//   object than the one that attains d1sq -- the two smallest of the per-object minimum distances; MEDT_EDT_NONE where the image
+//   has no such object.  Labels are not returned: under ties they are not unique, the two distances are.
+// Column pass: per pixel the nearest labelled pixel of its column, (g1, a), and the nearest one whose label is not a, (g2, b):
+// four planes of N*H*W int32 in `scratch`, g1 | a | g2 | b, EDT_FAR and label 0 where the column has none.
+// The shape of signed_edt_cols_kernel, with segments for its 32-row words: a work-item owns EDT2_SEG rows of one column, 16
+// neighbouring columns side by side in the lanes (8 above 2048 rows, so that the summaries fit 48 KB of LDS).  Its loads are
+// independent.  A sweep along a column carries the two-deep state (y_a, a), (y_b, b): a labelled pixel of label a moves y_a, any
+// other label pushes (y_a, a) into second place -- so y_b is always the last row whose label was not a.  A segment puts into LDS
+// what such a sweep would see of it from above and from below (its first labelled row and the first row of another label, from
+// either end); after the barrier a work-item builds the state entering its segment from the summaries above it, nearest first,
+// until both places are filled (edt2_offer_segment), sweeps its rows downward into registers, does the same from below and
+// merges the two pairs with edt2_take on the way up.  No sweep carries a dependency through global memory.
+// Row pass: the search of signed_edt_rows_kernel, fed both entries of every column, keeping the best pair of distinct labels.
+// Two entries per column suffice: if the second-nearest object reaches the pixel through a column where it is third or further
+// along the column, two other labels of that column are at least as close, one of them is not the nearest object's, and it
+// gives a distance no larger.
+// --------------------------------------------------------------------------- //
+constexpr int EDT2_SEG = 16;                                 // rows of a column a work-item owns
+constexpr int EDT2_ENTRIES = 2048;                           // (segment, column) pairs of a workgroup: 16 columns up to 2048 rows, 8 beyond
+
+// (b1, l1), (b2, l2): the two nearest so far, of distinct labels (label 0: none yet).  Offers (v, l); l == 0 is no candidate.
+__device__ __forceinline__ void edt2_take(int v, int l, int& b1, int& l1, int& b2, int& l2) {
+    if (l == 0) return;
+    if (l == l1) b1 = min(b1, v);
+    else if (v < b1) { b2 = b1; l2 = l1; b1 = v; l1 = l; }
+    else if (l == l2) b2 = min(b2, v);
+    else if (v < b2) { b2 = v; l2 = l; }
+}
+
+// One step of a sweep along a column: the state (ya, a), (yb, b) -- the last labelled row and its label, the last row whose label
+// was not a -- meets label l at row y.
+__device__ __forceinline__ void edt2_step(int y, int l, int& ya, int& a, int& yb, int& b) {
+    if (l > 0) {
+        if (l != a) { yb = ya; b = a; a = l; }
+        ya = y;
+    }
+}
+
+// A state that still lacks a or b is offered the labelled row r of label l (l <= 0: none); nearer rows were offered first.
+__device__ __forceinline__ void edt2_offer(int r, int l, int& ya, int& a, int& yb, int& b) {
+    const bool first = l > 0 && a == 0, second = l > 0 && a != 0 && b == 0 && l != a;     // (selects: the state stays in registers)
+    ya = first ? r : ya;
+    a = first ? l : a;
+    yb = second ? r : yb;
+    b = second ? l : b;
+}
+
+// ... a segment's summary as seen from outside: {rows r1 | r2 << 16, l1, l2}, (r1, l1) its labelled row nearest to the viewer and
+// (r2, l2) the nearest one whose label is not l1.
+__device__ __forceinline__ void edt2_offer_segment(int rows, int l1, int l2, int& ya, int& a, int& yb, int& b) {
+    edt2_offer(rows & 0xffff, l1, ya, a, yb, b);
+    edt2_offer(rows >> 16, l2, ya, a, yb, b);
+}
+
+__global__ __launch_bounds__(MEDT_THREADS) void object_edt2_cols_kernel(const int32_t* __restrict__ labels,
+                                                                        int32_t* __restrict__ scratch, int H, int W, int tiles,
+                                                                        int segs, int cpw, size_t plane) {
+    // per (segment, column): from the top {rows r1 | r2 << 16, l1, l2}, from the bottom the same
+    MEDT_STATIC_SHARED int32_t sum[6 * EDT2_ENTRIES];
+    const int n = blockIdx.x / tiles;
+    const int c = threadIdx.x % cpw, slot = threadIdx.x / cpw, slots = blockDim.x / cpw;
+    const int x = (blockIdx.x - n * tiles) * cpw + c;
+    const int32_t* lab = labels + (size_t)n * H * W + x;
+    if (x < W) {
+        for (int w = slot; w < segs; w += slots) {
+            const int y0 = w * EDT2_SEG;
+            int l[EDT2_SEG];
+#pragma unroll
+            for (int k = 0; k < EDT2_SEG; ++k) l[k] = y0 + k < H ? lab[(size_t)(y0 + k) * W] : 0;
+            int ya = 0, a = 0, yb = 0, b = 0;                  // from the top: the FIRST labelled row, the first of another label
+#pragma unroll
+            for (int k = 0; k < EDT2_SEG; ++k) edt2_offer(y0 + k, l[k], ya, a, yb, b);
+            int* e = sum + w * cpw + c;
+            e[0] = ya | (yb << 16);
+            e[EDT2_ENTRIES] = a;
+            e[2 * EDT2_ENTRIES] = b;
+            ya = a = yb = b = 0;                               // from the bottom
+#pragma unroll
+            for (int k = EDT2_SEG - 1; k >= 0; --k) edt2_offer(y0 + k, l[k], ya, a, yb, b);
+            e[3 * EDT2_ENTRIES] = ya | (yb << 16);
+            e[4 * EDT2_ENTRIES] = a;
+            e[5 * EDT2_ENTRIES] = b;
+        }
+    }
+    __syncthreads();
+    if (x >= W) return;
+    int32_t* G1 = scratch + (size_t)n * H * W + x;
+    int32_t *A = G1 + plane, *G2 = A + plane, *B = G2 + plane;
+    for (int w = slot; w < segs; w += slots) {
+        const int y0 = w * EDT2_SEG;
+        int l[EDT2_SEG], dn[EDT2_SEG], da[EDT2_SEG], db[EDT2_SEG];
+#pragma unroll
+        for (int k = 0; k < EDT2_SEG; ++k) l[k] = y0 + k < H ? lab[(size_t)(y0 + k) * W] : 0;
+        int ya = 0, a = 0, yb = 0, b = 0;                      // what the segments above hold, nearest first
+        for (int v = w - 1; v >= 0 && b == 0; --v) {
+            const int* e = sum + v * cpw + c;
+            edt2_offer_segment(e[3 * EDT2_ENTRIES], e[4 * EDT2_ENTRIES], e[5 * EDT2_ENTRIES], ya, a, yb, b);
+        }
+#pragma unroll
+        for (int k = 0; k < EDT2_SEG; ++k) {                   // downward: vertical distances (< 4096 each) and labels, in registers
+            const int y = y0 + k;
+            edt2_step(y, l[k], ya, a, yb, b);
+            dn[k] = (y - ya) | ((y - yb) << 16);
+            da[k] = a;
+            db[k] = b;
+        }
+        ya = a = yb = b = 0;                                   // what the segments below hold
+        for (int v = w + 1; v < segs && b == 0; ++v) {
+            const int* e = sum + v * cpw + c;
+            edt2_offer_segment(e[0], e[EDT2_ENTRIES], e[2 * EDT2_ENTRIES], ya, a, yb, b);
+        }
+#pragma unroll
+        for (int k = EDT2_SEG - 1; k >= 0; --k) {              // upward, merged with the downward pair
+            const int y = y0 + k;
+            if (y >= H) continue;
+            edt2_step(y, l[k], ya, a, yb, b);
+            const int d1 = dn[k] & 0xffff, d2 = dn[k] >> 16;
+            int b1 = da[k] ? d1 * d1 : EDT_FAR, l1 = da[k], b2 = db[k] ? d2 * d2 : EDT_FAR, l2 = db[k];
+            edt2_take((ya - y) * (ya - y), a, b1, l1, b2, l2);
+            edt2_take((yb - y) * (yb - y), b, b1, l1, b2, l2);
+            const size_t o = (size_t)y * W;
+            G1[o] = b1;
+            A[o] = l1;
+            G2[o] = b2;
+            B[o] = l2;
+        }
+    }
+}
+
+// Rows of the four planes in LDS, 256 / T rows per workgroup when a row needs only T < 256 work-items (as the signed row pass).
+__global__ __launch_bounds__(MEDT_THREADS) void object_edt2_rows_kernel(const int32_t* __restrict__ scratch,
+                                                                        int32_t* __restrict__ d1sq, int32_t* __restrict__ d2sq,
+                                                                        int W, int T, int rpb, int nrows, size_t plane) {
+    MEDT_STATIC_SHARED int32_t s1[MEDT_EDT_MAX_DIM], sa[MEDT_EDT_MAX_DIM], s2[MEDT_EDT_MAX_DIM], sb[MEDT_EDT_MAX_DIM];
+    const int rr = threadIdx.x / T, lx = threadIdx.x - rr * T;
+    const int rowi = blockIdx.x * rpb + rr;
+    const bool live = rr < rpb && rowi < nrows;
+    const size_t row = (size_t)(live ? rowi : 0) * W;
+    const int base = rr * T;                                    // rpb > 1 only when W <= T
+    if (live)
+        for (int x = lx; x < W; x += T) {
+            s1[base + x] = scratch[row + x];
+            sa[base + x] = scratch[plane + row + x];
+            s2[base + x] = scratch[2 * plane + row + x];
+            sb[base + x] = scratch[3 * plane + row + x];
+        }
+    __syncthreads();
+    if (!live) return;
+    for (int x = lx; x < W; x += T) {
+        int b1 = EDT_FAR, l1 = 0, b2 = EDT_FAR, l2 = 0;
+        edt2_take(s1[base + x], sa[base + x], b1, l1, b2, l2);
+        edt2_take(s2[base + x], sb[base + x], b1, l1, b2, l2);
+        const int reach = max(x, W - 1 - x);
+        for (int d = 1; d <= reach; ++d) {
+            const int dd = d * d;
+            if (dd >= b2) break;
+            if (x - d >= 0) {
+                const int i = base + x - d;
+                edt2_take(s1[i] + dd, sa[i], b1, l1, b2, l2);
+                edt2_take(s2[i] + dd, sb[i], b1, l1, b2, l2);
+            }
+            if (x + d < W) {
+                const int i = base + x + d;
+                edt2_take(s1[i] + dd, sa[i], b1, l1, b2, l2);
+                edt2_take(s2[i] + dd, sb[i], b1, l1, b2, l2);
+            }
+        }
+        d1sq[row + x] = b1 >= EDT_FAR ? MEDT_EDT_NONE : b1;
+        d2sq[row + x] = b2 >= EDT_FAR ? MEDT_EDT_NONE : b2;
+    }
+}
+
+int object_edt2(const int32_t* labels, int32_t* scratch, int32_t* d1sq, int32_t* d2sq, int N, int H, int W, hipStream_t s) {
+    const int segs = cdiv(H, EDT2_SEG), cpw = segs * 16 <= EDT2_ENTRIES ? 16 : 8, tiles = cdiv(W, cpw);
+    const size_t plane = (size_t)N * H * W;
+    const unsigned cthreads = (unsigned)min(max(cdiv(segs * cpw, 64) * 64, 64), MEDT_THREADS);
+    hipLaunchKernelGGL(object_edt2_cols_kernel, dim3((unsigned)N * tiles), dim3(cthreads), 0, s, labels, scratch, H, W, tiles, segs,
+                       cpw, plane);
+    if (int rc = launch_status("object_edt2_cols")) return rc;
+    const int T = (int)edt_threads(W), rpb = W <= T ? MEDT_THREADS / T : 1, nrows = N * H;
+    hipLaunchKernelGGL(object_edt2_rows_kernel, dim3((unsigned)cdiv(nrows, rpb)), dim3((unsigned)(T * rpb)), 0, s, scratch, d1sq,
+                       d2sq, W, T, rpb, nrows, plane);
+    return launch_status("object_edt2_rows");
+}
+
+// --------------------------------------------------------------------------- //
+// Border term of the loss (U-Net's weight map for touching objects, as an additive term):
+//   R = mean over images n of ( sum over valid p of e_n(p) nll_n(p) / max(1, V_n) ),  nll = -log softmax(logits)[target],
+//   e = exp(-(sqrt(d1sq) + sqrt(d2sq))^2 / (2 sigma^2)) at the pixels outside F = {target == fg} whose d2sq is not
+//   MEDT_EDT_NONE, 0 elsewhere; computed from the integers on the fly.  Valid pixels, V_n, the grid, the partials [N][bpi][2]
+//   = {sum e nll, V} and `out` are the boundary term's, and so is the finalize (boundary_finalize_kernel, w0 for alpha):
+//   out = [base + w0 R (w0 R when base is NULL), R, w0, 1 / (N max(1, V_n)) for n < N]
+// --------------------------------------------------------------------------- //
+__device__ __forceinline__ float border_e(int64_t t, int fg, int d1, int d2, float inv2s2) {
+    if (t == fg || d2 == MEDT_EDT_NONE) return 0.f;
+    const float s = sqrtf((float)d1) + sqrtf((float)d2);
+    return __expf(-(s * s) * inv2s2);
+}
+
+__global__ __launch_bounds__(MEDT_THREADS) void border_fwd_kernel(const float* __restrict__ logits,
+                                                                  const int64_t* __restrict__ target,
+                                                                  const int32_t* __restrict__ d1sq,
+                                                                  const int32_t* __restrict__ d2sq, float* __restrict__ partials,
+                                                                  int K, int HW, int bpi, int fg, int ignore, float inv2s2) {
+    MEDT_STATIC_SHARED float red[MEDT_WAVES * 2];
+    const int n = blockIdx.x / bpi;
+    const int p = (blockIdx.x - n * bpi) * MEDT_THREADS + threadIdx.x;
+    float v[2] = {0.f, 0.f};
+    if (p < HW) {
+        const int64_t t = target[(size_t)n * HW + p];
+        if (t != ignore && t >= 0 && t < K) {
+            v[1] = 1.f;
+            const float e = border_e(t, fg, d1sq[(size_t)n * HW + p], d2sq[(size_t)n * HW + p], inv2s2);
+            if (e != 0.f) {
+                const float* lp = logits + (size_t)n * K * HW + p;
+                float m = lp[0];
+                for (int k = 1; k < K; ++k) m = fmaxf(m, lp[(size_t)k * HW]);
+                float sum = 0.f;
+                for (int k = 0; k < K; ++k) sum += __expf(lp[(size_t)k * HW] - m);
+                v[0] = e * (m + __logf(sum) - lp[(size_t)t * HW]);
+            }
+        }
+    }
+    block_sum<2>(v, red, partials + (size_t)blockIdx.x * 2);
+}
+
+// dlogits[n,k,p] (+)= dloss w0 e / (N max(1, V_n)) * (p_k - delta_k,t)
+template <bool ACC>
+__global__ __launch_bounds__(MEDT_THREADS) void border_bwd_kernel(const float* __restrict__ logits,
+                                                                  const int64_t* __restrict__ target,
+                                                                  const int32_t* __restrict__ d1sq,
+                                                                  const int32_t* __restrict__ d2sq, const float* __restrict__ out,
+                                                                  const float* __restrict__ dloss, float* __restrict__ dlogits,
+                                                                  int K, int HW, int bpi, int fg, int ignore, float inv2s2) {
+    const int n = blockIdx.x / bpi;
+    const int p = (blockIdx.x - n * bpi) * MEDT_THREADS + threadIdx.x;
+    if (p >= HW) return;
+    const int64_t t = target[(size_t)n * HW + p];
+    const float* lp = logits + (size_t)n * K * HW + p;
+    float* dp = dlogits + (size_t)n * K * HW + p;
+    const bool valid = t != ignore && t >= 0 && t < K;
+    const float e = valid ? border_e(t, fg, d1sq[(size_t)n * HW + p], d2sq[(size_t)n * HW + p], inv2s2) : 0.f;
+    if (e == 0.f) {                                           // not valid, inside F, or no second object: no gradient
+        if (!ACC)
+            for (int k = 0; k < K; ++k) dp[(size_t)k * HW] = 0.f;
+        return;                                               // ACC: the region loss's backward wrote this pixel
+    }
+    float m = lp[0];
+    for (int k = 1; k < K; ++k) m = fmaxf(m, lp[(size_t)k * HW]);
+    float sum = 0.f;
+    for (int k = 0; k < K; ++k) sum += __expf(lp[(size_t)k * HW] - m);
+    const float inv = 1.f / sum;
+    const float c = (dloss ? dloss[0] : 1.f) * out[2] * out[3 + n] * e;
+    for (int k = 0; k < K; ++k) {
+        const float pk = __expf(lp[(size_t)k * HW] - m) * inv;
+        const float gk = c * (pk - (k == t ? 1.f : 0.f));
+        dp[(size_t)k * HW] = ACC ? dp[(size_t)k * HW] + gk : gk;
+    }
+}
+
+int border_fwd(const float* logits, const int64_t* target, const int32_t* d1sq, const int32_t* d2sq, float sigma, const float* w0,
+               const float* base, float* partials, float* out, int N, int K, int HW, int fg, int ignore, hipStream_t s) {
+    const int bpi = seg_loss_bpi(HW);
+    const float inv2s2 = (float)(1.0 / (2.0 * (double)sigma * (double)sigma));
+    hipLaunchKernelGGL(border_fwd_kernel, dim3((unsigned)N * bpi), dim3(MEDT_THREADS), 0, s, logits, target, d1sq, d2sq, partials,
+                       K, HW, bpi, fg, ignore, inv2s2);
+    if (int rc = launch_status("border_fwd")) return rc;
+    hipLaunchKernelGGL(boundary_finalize_kernel, dim3(1), dim3(MEDT_THREADS), 0, s, partials, w0, base, out, N, bpi);
+    return launch_status("border_finalize");
+}
+
+int border_bwd(const float* logits, const int64_t* target, const int32_t* d1sq, const int32_t* d2sq, float sigma, const float* out,
+               const float* dloss, float* dlogits, int N, int K, int HW, int fg, int ignore, int accumulate, hipStream_t s) {
+    const int bpi = seg_loss_bpi(HW);
+    const float inv2s2 = (float)(1.0 / (2.0 * (double)sigma * (double)sigma));
+    const dim3 grid((unsigned)N * bpi), block(MEDT_THREADS);
+    if (accumulate)
+        hipLaunchKernelGGL(border_bwd_kernel<true>, grid, block, 0, s, logits, target, d1sq, d2sq, out, dloss, dlogits, K, HW, bpi,
+                           fg, ignore, inv2s2);
+    else
+        hipLaunchKernelGGL(border_bwd_kernel<false>, grid, block, 0, s, logits, target, d1sq, d2sq, out, dloss, dlogits, K, HW, bpi,
+                           fg, ignore, inv2s2);
+    return launch_status("border_bwd");
+}
+
 }  // namespace medt

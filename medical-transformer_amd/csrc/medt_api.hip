@@ -1076,6 +1076,44 @@ int medt_boundary_bwd(const float* logits, const int64_t* target, const int32_t*
     return boundary_bwd(logits, target, sd2, out, dloss, dlogits, N, K, HW, fg, ignore_index, accumulate, (hipStream_t)stream);
 }
 
+int medt_object_edt2(const int32_t* labels, int32_t* scratch, int32_t* d1sq, int32_t* d2sq, int N, int H, int W, void* stream) {
+    if (const int rc = edt_geometry("object_edt2", N, H, W)) return rc;
+    if (!labels || !scratch || !d1sq || !d2sq || d1sq == d2sq || scratch == d1sq || scratch == d2sq) {
+        set_error("object_edt2: null labels, scratch, d1sq or d2sq, or two of the three outputs are one buffer"); return MEDT_EINVAL;
+    }
+    return object_edt2(labels, scratch, d1sq, d2sq, N, H, W, (hipStream_t)stream);
+}
+
+// medt_border_*: the sizes and the foreground class as medt_boundary_*, and a positive finite sigma
+static int border_args(const char* what, int N, int K, int HW, int fg, float sigma) {
+    if (int rc = boundary_args(what, N, K, HW, fg)) return rc;
+    if (!(sigma > 0.f) || !(sigma <= 3.0e38f)) { set_error("%s: sigma %g: a positive finite width expected", what, (double)sigma); return MEDT_EINVAL; }
+    return MEDT_OK;
+}
+size_t medt_border_workspace(int N, int HW) {
+    if (boundary_args("border workspace", N, 2, HW, 0)) return 0;
+    return boundary_partials(N, HW);
+}
+size_t medt_border_out_floats(int N) {
+    if (boundary_args("border out_floats", N, 2, 1, 0)) return 0;
+    return boundary_out_floats(N);
+}
+int medt_border_fwd(const float* logits, const int64_t* target, const int32_t* d1sq, const int32_t* d2sq, float sigma,
+                    const float* w0, const float* base, float* partials, float* out, int N, int K, int HW, int fg,
+                    int ignore_index, void* stream) {
+    if (!logits || !target || !d1sq || !d2sq || !w0 || !partials || !out) { set_error("border fwd: null pointer"); return MEDT_EINVAL; }
+    if (int rc = border_args("border fwd", N, K, HW, fg, sigma)) return rc;
+    return border_fwd(logits, target, d1sq, d2sq, sigma, w0, base, partials, out, N, K, HW, fg, ignore_index, (hipStream_t)stream);
+}
+int medt_border_bwd(const float* logits, const int64_t* target, const int32_t* d1sq, const int32_t* d2sq, float sigma,
+                    const float* out, const float* dloss, float* dlogits, int N, int K, int HW, int fg, int ignore_index,
+                    int accumulate, void* stream) {
+    if (!logits || !target || !d1sq || !d2sq || !out || !dlogits) { set_error("border bwd: null pointer"); return MEDT_EINVAL; }
+    if (int rc = border_args("border bwd", N, K, HW, fg, sigma)) return rc;
+    return border_bwd(logits, target, d1sq, d2sq, sigma, out, dloss, dlogits, N, K, HW, fg, ignore_index, accumulate,
+                      (hipStream_t)stream);
+}
+
 static int label_geometry(const char* what, int N, int H, int W) {
     if (N < 1 || H < 1 || W < 1) {
         set_error("%s: bad arguments (%d images of %d x %d)", what, N, H, W); return MEDT_EINVAL;

@@ -140,6 +140,13 @@ int boundary_fwd(const float* logits, const int64_t* target, const int32_t* sd2,
                  float* partials, float* out, int N, int K, int HW, int fg, int ignore, hipStream_t s);
 int boundary_bwd(const float* logits, const int64_t* target, const int32_t* sd2, const float* out, const float* dloss,
                  float* dlogits, int N, int K, int HW, int fg, int ignore, int accumulate, hipStream_t s);
+// squared distances to the two nearest objects of a label map (two launches) and the border term of the loss on them (medt_abi.h);
+// the border term's workspace and `out` are the boundary term's
+int object_edt2(const int32_t* labels, int32_t* scratch, int32_t* d1sq, int32_t* d2sq, int N, int H, int W, hipStream_t s);
+int border_fwd(const float* logits, const int64_t* target, const int32_t* d1sq, const int32_t* d2sq, float sigma, const float* w0,
+               const float* base, float* partials, float* out, int N, int K, int HW, int fg, int ignore, hipStream_t s);
+int border_bwd(const float* logits, const int64_t* target, const int32_t* d1sq, const int32_t* d2sq, float sigma, const float* out,
+               const float* dloss, float* dlogits, int N, int K, int HW, int fg, int ignore, int accumulate, hipStream_t s);
 // connected-component labelling, component tables, table-driven select (label.hip; medt_abi.h)
 size_t label_workspace_bytes(int N, int H, int W);
 int label_components(const uint8_t* mask, int32_t* labels, int32_t* count, void* workspace, int N, int H, int W, int connectivity,

@@ -162,6 +162,11 @@ SIGNATURES = {
     "medt_boundary_out_floats": (C.c_size_t, [C.c_int]),
     "medt_boundary_fwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p]),
     "medt_boundary_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p]),
+    "medt_object_edt2": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
+    "medt_border_workspace": (C.c_size_t, [C.c_int, C.c_int]),
+    "medt_border_out_floats": (C.c_size_t, [C.c_int]),
+    "medt_border_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
+    "medt_border_bwd": (C.c_int, [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p]),
     "medt_label_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "medt_label_components": (C.c_int, [C.c_void_p] * 4 + [C.c_size_t] + [C.c_int] * 5 + [C.c_void_p]),
     "medt_label_tables": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),

@@ -610,6 +610,132 @@ def seg_boundary_loss(logits, target, alpha, weight=None, ce=1.0, dice=0.0, eps=
 
 
 # --------------------------------------------------------------------------- #
+# border weight for touching objects (Ronneberger et al., U-Net, 2015) on the components of the step's own label map
+# --------------------------------------------------------------------------- #
+class SegBorderFn(torch.autograd.Function):
+    """region loss (medt_seg_loss_*, unchanged; left out when ce == dice == 0) + w0 * border term as ONE node, as SegBoundaryFn:
+    the finalize adds the region loss on the device, the border backward adds into the region backward's dlogits.  The maps come
+    from the targets inside the node: {target == fg} as a uint8 mask (torch), label() -> object_edt2_sq(); nothing syncs."""
+
+    @staticmethod
+    def forward(ctx, logits, target, w0, weight, ce, dice, eps, fg, connectivity, ignore_index, sigma):
+        _require_device(logits)
+        lib = L.lib()
+        logits, target = logits.contiguous(), target.contiguous()
+        N, K = logits.shape[0], logits.shape[1]
+        HW = logits[0, 0].numel()
+        region = ce != 0.0 or dice != 0.0
+        rout = None
+        if region:
+            nws, nout = lib.medt_seg_loss_workspace(N, K, HW), lib.medt_seg_loss_out_floats(N, K)
+            if not nws or not nout:
+                raise L.MedtError(f"seg_border_loss: {lib.medt_last_error().decode()}")
+            partials = torch.empty((nws,), device=logits.device, dtype=torch.float32)
+            rout = torch.empty((nout,), device=logits.device, dtype=torch.float32)
+            L.check(lib.medt_seg_loss_fwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), partials.data_ptr(), rout.data_ptr(),
+                                          N, K, HW, ignore_index, ce, dice, eps, _stream()), "medt_seg_loss_fwd")
+        mask = torch.empty(target.shape, device=target.device, dtype=torch.uint8)
+        torch.eq(target, fg, out=mask)                             # F as the uint8 mask label() takes, in one launch
+        if fg == ignore_index:                                     # an ignored pixel is not in F
+            mask.zero_()
+        labels, _ = label(mask, connectivity)
+        d1, d2 = object_edt2_sq(labels)
+        nws, nout = lib.medt_border_workspace(N, HW), lib.medt_border_out_floats(N)
+        if not nws or not nout:
+            raise L.MedtError(f"border_loss: {lib.medt_last_error().decode()}")
+        bparts = torch.empty((nws,), device=logits.device, dtype=torch.float32)
+        bout = torch.empty((nout,), device=logits.device, dtype=torch.float32)
+        L.check(lib.medt_border_fwd(logits.data_ptr(), target.data_ptr(), d1.data_ptr(), d2.data_ptr(), sigma, w0.data_ptr(),
+                                    L.ptr(rout), bparts.data_ptr(), bout.data_ptr(), N, K, HW, fg, ignore_index, _stream()),
+                "medt_border_fwd")
+        saved = [logits, target, d1, d2, bout] + ([rout] if region else []) + ([weight] if weight is not None else [])
+        ctx.save_for_backward(*saved)
+        ctx.cfg = (ce, dice, eps, fg, ignore_index, sigma, region, weight is not None)
+        loss = bout[0]
+        outs = (bout, rout) if region else (bout,)
+        ctx.mark_non_differentiable(*outs)
+        ctx.set_materialize_grads(False)
+        return (loss,) + outs
+
+    @staticmethod
+    def backward(ctx, dloss, *_):
+        if dloss is None:
+            return (None,) * 11
+        lib = L.lib()
+        ce, dice, eps, fg, ignore_index, sigma, region, weighted = ctx.cfg
+        logits, target, d1, d2, bout, *rest = ctx.saved_tensors
+        rout = rest.pop(0) if region else None
+        weight = rest.pop(0) if weighted else None
+        N, K = logits.shape[0], logits.shape[1]
+        HW = logits[0, 0].numel()
+        dloss = dloss.contiguous().float()
+        dlogits = torch.empty_like(logits)
+        if region:
+            L.check(lib.medt_seg_loss_bwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), rout.data_ptr(), dloss.data_ptr(),
+                                          dlogits.data_ptr(), N, K, HW, ignore_index, ce, dice, eps, _stream()),
+                    "medt_seg_loss_bwd")
+        L.check(lib.medt_border_bwd(logits.data_ptr(), target.data_ptr(), d1.data_ptr(), d2.data_ptr(), sigma, bout.data_ptr(),
+                                    dloss.data_ptr(), dlogits.data_ptr(), N, K, HW, fg, ignore_index, int(region), _stream()),
+                "medt_border_bwd")
+        return (dlogits,) + (None,) * 10
+
+
+def _border_args(what, logits, target, w0, sigma, fg, connectivity):
+    """_boundary_args for w0, + sigma and the connectivity -> (w0 tensor, sigma)."""
+    w0 = _boundary_args(what, logits, target, w0, fg)
+    sigma = float(sigma)
+    if not 0.0 < sigma < float("inf"):
+        raise L.MedtError(f"{what}: sigma must be positive and finite (got {sigma})")
+    if connectivity not in (4, 8):
+        raise L.MedtError(f"{what}: connectivity {connectivity!r} (4 or 8)")
+    return w0, sigma
+
+
+def border_loss(logits, target, w0, sigma=5.0, fg=1, connectivity=8, ignore_index=-100):
+    """w0 * R, the border term alone, of (N,K,H,W) float32 logits against (N,H,W) int64 class indices:
+    R = mean over images n of ( sum over the valid pixels p of e_n(p) * nll_n(p) / max(1, V_n) ), nll = -log softmax(logits)[target],
+    e = exp(-(d1 + d2)^2 / (2 sigma^2)) at the pixels outside F = {target == fg} that have two objects to be between, 0 elsewhere;
+    d1, d2: the distances to the nearest and the second-nearest connected component of F (`connectivity` 4 or 8), from
+    label() and object_edt2_sq() on the device, from the step's own label map.  U-Net's weight map w = 1 + w0 e applied to the
+    cross entropy is mean cross entropy + w0 R.  Valid pixels as boundary_loss(); an ignored pixel is not in F.  w0: a one-element
+    float32 device tensor, READ ON THE DEVICE by the kernels (refill it in place and a captured step follows), or a number.
+    No host sync, no float atomics.  loss._medt_border_out = [w0 R, R, w0, ...]."""
+    w0, sigma = _border_args("border_loss", logits, target, w0, sigma, fg, connectivity)
+    loss, bout = SegBorderFn.apply(logits, target, w0, None, 0.0, 0.0, 1.0, int(fg), int(connectivity), int(ignore_index), sigma)
+    loss._medt_border_out = bout
+    return loss
+
+
+def seg_border_loss(logits, target, w0, sigma=5.0, weight=None, ce=1.0, dice=0.0, eps=1.0, fg=1, connectivity=8, ignore_index=-100):
+    """seg_loss(logits, target, weight, ce, dice, eps, ignore_index) + w0 * R with R of border_loss(), as one autograd node: the
+    region term runs through the unchanged medt_seg_loss_* entry points, the border finalize adds it on the device and the border
+    backward adds into the dlogits the region backward has just written.  With w0 == 0 loss and gradient are seg_loss's, bit for
+    bit.  loss._medt_ce_out is the region term's `out` (so TrainStep.check_targets() works as with seg_loss),
+    loss._medt_border_out = [loss, R, w0, ...]."""
+    w0, sigma = _border_args("seg_border_loss", logits, target, w0, sigma, fg, connectivity)
+    K = logits.shape[1]
+    if weight is not None:
+        if (not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.dim() != 1 or weight.numel() != K
+                or weight.device != logits.device):
+            raise L.MedtError(f"seg_border_loss: weight must be a float32 tensor of {K} class weights on the logits' device")
+        weight = weight.detach().contiguous()
+    ce, dice, eps = float(ce), float(dice), float(eps)
+    if ce == 0.0 and dice == 0.0:
+        raise L.MedtError("seg_border_loss: no region term (ce == dice == 0): border_loss() is the term alone")
+    if dice != 0.0 and not 2 <= K <= 8:
+        raise L.MedtError(f"seg_border_loss: soft Dice needs 2 <= K <= 8 classes (K = {K})")
+    if not eps >= 0.0:
+        raise L.MedtError("seg_border_loss: eps >= 0 expected")
+    loss, bout, rout = SegBorderFn.apply(logits, target, w0, weight, ce, dice, eps, int(fg), int(connectivity), int(ignore_index),
+                                         sigma)
+    loss._medt_ce_out = rout
+    loss._medt_border_out = bout
+    if CHECK_TARGETS and not torch.cuda.is_current_stream_capturing():
+        raise_on_bad_targets(rout, K)
+    return loss
+
+
+# --------------------------------------------------------------------------- #
 # segmentation scoring (replaces performancemetrics_*.m)
 # --------------------------------------------------------------------------- #
 def seg_counts(logits, target, threshold=0.5):
@@ -820,6 +946,30 @@ def signed_edt_sq(target, fg=1, ignore_index=-100, out=None):
     L.check(L.lib().medt_signed_edt(t.data_ptr(), g2.data_ptr(), sd2.data_ptr(), N, H, W, fg, ignore_index, _stream()),
             "medt_signed_edt")
     return sd2
+
+
+def object_edt2_sq(labels, out=None):
+    """int32 (N,H,W) or (H,W) label map (0: no object, l > 0: object l, as label() writes it) -> (d1sq, d2sq), int32 of the same
+    shape: the exact squared Euclidean distances to the nearest object (0 inside one) and to the nearest object other than that
+    one -- the two smallest of the per-object minimum distances; inside object l, d2sq is the distance to the nearest other
+    object.  EDT_NONE where there is no such object: d1sq in an image without objects, d2sq in an image with fewer than two.
+    Bit-identical from run to run; at most 4096 pixels per side.  out: a pair of contiguous int32 tensors to write into (any
+    alignment: the kernels use element accesses)."""
+    _require_device(labels.new_empty(0, dtype=torch.float32))      # (the device check; the label map itself is int32)
+    if labels.dtype != torch.int32 or labels.dim() not in (2, 3):
+        raise L.MedtError("object_edt2_sq: an int32 (N,H,W) or (H,W) label map expected")
+    if labels.numel() == 0:
+        raise L.MedtError("object_edt2_sq: empty label map")
+    if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 2):
+        raise L.MedtError("object_edt2_sq: out must be a pair (d1sq, d2sq) of int32 tensors")
+    lab = labels.contiguous().reshape(-1, *labels.shape[-2:])
+    N, H, W = lab.shape
+    d1 = _edt_out("object_edt2_sq", None if out is None else out[0], labels)
+    d2 = _edt_out("object_edt2_sq", None if out is None else out[1], labels)
+    scratch = torch.empty((4,) + tuple(lab.shape), device=lab.device, dtype=torch.int32)       # g1 | a | g2 | b (medt_abi.h)
+    L.check(L.lib().medt_object_edt2(lab.data_ptr(), scratch.data_ptr(), d1.data_ptr(), d2.data_ptr(), N, H, W, _stream()),
+            "medt_object_edt2")
+    return d1, d2
 
 
 # --------------------------------------------------------------------------- #

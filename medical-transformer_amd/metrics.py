@@ -67,6 +67,33 @@ class BoundaryLoss(torch.nn.Module):
                                           eps=self.eps, fg=self.fg, ignore_index=self.ignore_index)
 
 
+class BorderLoss(torch.nn.Module):
+    """ce * (class-weighted) cross entropy + dice * soft Dice + w0 * the border term for touching objects (the weight map of
+    Ronneberger et al., U-Net, 2015, w0 exp(-(d1 + d2)^2 / (2 sigma^2)), applied to the cross entropy of the pixels between two
+    objects of the class `fg`): medt_amd.seg_border_loss has the formulas.  The objects are the connected components of the label
+    map the step holds on the device (after the device-side augmentation, where there is one), not of the dataset's masks.
+
+    `w0` is a registered float32 buffer of one element that the kernels read on the device: set_w0() fills it in place, so a
+    captured step follows a change without another capture."""
+
+    def __init__(self, w0=10.0, sigma=5.0, weight=None, ce=1.0, dice=0.0, eps=1.0, fg=1, connectivity=8, ignore_index=-100):
+        super().__init__()
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32).reshape(-1)
+        self.register_buffer("weight", weight)
+        self.register_buffer("w0", torch.full((1,), float(w0), dtype=torch.float32))
+        self.sigma, self.ce, self.dice, self.eps = float(sigma), float(ce), float(dice), float(eps)
+        self.fg, self.connectivity, self.ignore_index = int(fg), int(connectivity), ignore_index
+
+    def set_w0(self, v):
+        self.w0.fill_(float(v))
+
+    def forward(self, y_input, y_target):
+        return medt_amd.seg_border_loss(y_input, y_target, self.w0, sigma=self.sigma, weight=self.weight, ce=self.ce,
+                                        dice=self.dice, eps=self.eps, fg=self.fg, connectivity=self.connectivity,
+                                        ignore_index=self.ignore_index)
+
+
 def classwise_iou(output, gt):
     dims = (0, *range(2, len(output.shape)))
     onehot = torch.zeros_like(output).scatter_(1, gt[:, None, :], 1)

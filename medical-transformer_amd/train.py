@@ -16,6 +16,10 @@ Differences, all host-side plumbing:
   * --loss ce+boundary / dice+boundary / ce+dice+boundary add the boundary loss of Kervadec et al. (metrics.BoundaryLoss; the
     signed distance map is computed on the GPU from the batch's own masks); its weight starts at --boundary_alpha, grows by
     --boundary_step after every epoch up to --boundary_max, and is printed as `boundary alpha` before the epoch line;
+  * --loss ce+border / dice+border / ce+dice+border add U-Net's border weight for touching objects as a term of the loss
+    (metrics.BorderLoss; the objects are the connected components of the batch's own masks, labelled and measured on the GPU):
+    --border_w0 is its weight, --border_sigma its width in pixels, --border_connectivity {4,8} what counts as one object
+    (printed once as `border w0 .. sigma .. connectivity ..`);
   * --aug on moves the joint transform to the GPU (medt_amd.augment: the uint8 image is uploaded, two kernels crop, flip,
     jitter and map it); --aug_jitter "b,c,s,h" and --aug_affine P add the colour jitter and the random affine map the
     reference's JointTransform2D has and its train.py never enables; --aug off (the default) is the host transform as before;
@@ -30,7 +34,7 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 
 import lib
-from metrics import BoundaryLoss, DiceCELoss, LogNLLLoss
+from metrics import BorderLoss, BoundaryLoss, DiceCELoss, LogNLLLoss
 from medt_amd import dp
 from medt_amd.data import DevicePrefetcher, imwrite, make_synthetic_dataset
 from medt_amd.optim import FlatAdam
@@ -61,12 +65,17 @@ parser.add_argument('--device', default='cuda', type=str)
 parser.add_argument('--gray', default='no', type=str)
 parser.add_argument('--synthetic', type=int, default=0, help='write this many synthetic PNG pairs into the dataset dirs first')
 parser.add_argument('--eager', action='store_true', help='no hipGraph replay')
-parser.add_argument('--loss', default='ce', choices=['ce', 'dice', 'ce+dice', 'ce+boundary', 'dice+boundary', 'ce+dice+boundary'],
-                    help='cross entropy, soft Dice or their sum, +boundary: plus the boundary loss (default: ce)')
+parser.add_argument('--loss', default='ce', choices=['ce', 'dice', 'ce+dice', 'ce+boundary', 'dice+boundary', 'ce+dice+boundary',
+                                                      'ce+border', 'dice+border', 'ce+dice+border'],
+                    help='cross entropy, soft Dice or their sum, +boundary: plus the boundary loss, +border: plus the border weight '
+                         'for touching objects (default: ce)')
 parser.add_argument('--class_weights', default=None, type=str, help='comma-separated class weights of the cross entropy, e.g. "1,3"')
 parser.add_argument('--boundary_alpha', default=None, type=float, help='with a +boundary loss: weight of the boundary term in the first epoch (default: 0.01)')
 parser.add_argument('--boundary_step', default=None, type=float, help='with a +boundary loss: added to the weight after every epoch (default: 0.01)')
 parser.add_argument('--boundary_max', default=None, type=float, help='with a +boundary loss: the weight stops growing here (default: 1.0)')
+parser.add_argument('--border_w0', default=None, type=float, help='with a +border loss: weight of the border term (default: 10)')
+parser.add_argument('--border_sigma', default=None, type=float, help='with a +border loss: width of the border weight in pixels (default: 5)')
+parser.add_argument('--border_connectivity', default=None, type=int, choices=[4, 8], help='with a +border loss: connectivity of the objects (default: 8)')
 
 NUM_CLASSES = 2          # every network of lib.models ends in a 2-channel adjust convolution
 
@@ -89,9 +98,24 @@ def boundary_alpha(sched, epoch):
     return min(sched["max"], sched["alpha"] + sched["step"] * epoch)
 
 
-def make_criterion(loss, class_weights, boundary=None):
+def make_border(loss, w0, sigma, connectivity):
+    """None without a +border loss, else the settings of the border term: its weight, its width, the objects' connectivity."""
+    if not loss.endswith("+border"):
+        if w0 is not None or sigma is not None or connectivity is not None:
+            raise SystemExit("--border_w0 / --border_sigma / --border_connectivity belong to the border term: "
+                             "use --loss ce+border, dice+border or ce+dice+border")
+        return None
+    border = {"w0": 10.0 if w0 is None else w0, "sigma": 5.0 if sigma is None else sigma,
+              "connectivity": 8 if connectivity is None else connectivity}
+    if not (border["w0"] >= 0.0 and 0.0 < border["sigma"] < float("inf")):
+        raise SystemExit("--border_w0 >= 0 and --border_sigma > 0 expected, got %r" % (border,))
+    return border
+
+
+def make_criterion(loss, class_weights, boundary=None, border=None):
     weight = None
     region = loss[:-len("+boundary")] if loss.endswith("+boundary") else loss
+    region = region[:-len("+border")] if region.endswith("+border") else region
     if class_weights is not None:
         try:
             weight = [float(w) for w in class_weights.split(",")]
@@ -102,6 +126,10 @@ def make_criterion(loss, class_weights, boundary=None):
         if region == "dice":
             raise SystemExit("--class_weights weigh the cross entropy: use --loss ce or ce+dice")
         weight = torch.tensor(weight, dtype=torch.float32)
+    if loss.endswith("+border"):
+        border = make_border(loss, None, None, None) if border is None else border
+        return BorderLoss(w0=border["w0"], sigma=border["sigma"], connectivity=border["connectivity"], weight=weight,
+                          ce=0.0 if region == "dice" else 1.0, dice=0.0 if region == "ce" else 1.0)
     if region != loss:
         return BoundaryLoss(alpha=0.01 if boundary is None else boundary["alpha"], weight=weight, ce=0.0 if region == "dice" else 1.0,
                             dice=0.0 if region == "ce" else 1.0)
@@ -133,7 +161,8 @@ def make_augment(aug, aug_jitter, aug_affine):
 def main():
     args = parser.parse_args()
     boundary = make_boundary(args.loss, args.boundary_alpha, args.boundary_step, args.boundary_max)    # (so do --boundary_* alone)
-    criterion = make_criterion(args.loss, args.class_weights, boundary)      # (a bad --class_weights ends the run before any work)
+    border = make_border(args.loss, args.border_w0, args.border_sigma, args.border_connectivity)        # (and --border_* alone)
+    criterion = make_criterion(args.loss, args.class_weights, boundary, border)      # (a bad --class_weights ends the run before any work)
     augment = make_augment(args.aug, args.aug_jitter, args.aug_affine)              # (so does a bad --aug_* combination)
     direc, modelname, imgsize = args.direc, args.modelname, args.imgsize
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -195,6 +224,8 @@ def main():
     infer_step = InferStep(model, use_graph=not args.eager)
     if rank == 0:
         print("Total_params: {}".format(sum(p.numel() for p in model.parameters() if p.requires_grad)))
+    if rank == 0 and border is not None:
+        print('border w0 {:.4f} sigma {:.4f} connectivity {}'.format(border["w0"], border["sigma"], border["connectivity"]))
 
     seed = 3000
     np.random.seed(seed)
