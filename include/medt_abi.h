@@ -297,6 +297,18 @@ size_t medt_conv_workspace_bytes(const medt_conv_desc*);   /* max over fwd and b
 int medt_conv_block_fwd(const medt_conv_desc*, const float* x, const float* w, const float* bias,
                         const medt_bn_ptrs* bn, const float* res, float* z, float* y, float* stats,
                         void* workspace, size_t workspace_bytes, void* stream);
+/* Two INDEPENDENT blocks A and B (neither reads what the other writes) in side-by-side launches: the arguments of
+ * medt_conv_block_fwd twice, each member with its own workspace sized by medt_conv_workspace_bytes.  Every output (z, y, stats, the
+ * recorded jobs of a bound queue, A's before B's) is bit-identical to medt_conv_block_fwd(A) followed by medt_conv_block_fwd(B).
+ * Where both members take the same kernel family (1x1 + BatchNorm: the fused small-group kernel, or convolution + statistics/apply)
+ * each stage is ONE launch whose grid carries both problems; any other combination runs the two single plans.  Built for the first
+ * unit of a layer, where conv_down and the downsample path read the same x (axialnet.py:327, 339-340). */
+int medt_conv_block_pair_fwd(const medt_conv_desc* da, const float* xa, const float* wa, const float* biasa,
+                             const medt_bn_ptrs* bna, const float* resa, float* za, float* ya, float* statsa,
+                             void* workspace_a, size_t workspace_a_bytes,
+                             const medt_conv_desc* db, const float* xb, const float* wb, const float* biasb,
+                             const medt_bn_ptrs* bnb, const float* resb, float* zb, float* yb, float* statsb,
+                             void* workspace_b, size_t workspace_b_bytes, void* stream);
 /* dx, dbias, dres may be NULL (not needed).  dw, dbn_weight, dbn_bias are written, not accumulated.
  * dx_add (optional, same shape as dx): dx = conv-backward + dx_add.  The input of an AxialBlock feeds conv_down AND the
  * residual / downsample path (axialnet.py:327,339-340) and the decoder skips (:494-500); the reference's autograd sums

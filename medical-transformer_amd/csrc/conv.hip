@@ -17,15 +17,15 @@ namespace medt {
 // of the deep LoGo layers still fill the wave.  Optional per-channel [sum, sum^2] partials are laid out
 // [group][part][Cout][2] with part = 256-position chunk inside the group (BatchNorm statistics).
 // --------------------------------------------------------------------------- //
+// (the body takes its block coordinates as arguments: conv1x1_fwd_pair_kernel below runs two problems in one grid)
 template <int K, int OT>
-__global__ __launch_bounds__(MEDT_THREADS) void conv2d_fwd_kernel(
+__device__ __forceinline__ void conv2d_fwd_body(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ y,
     float* __restrict__ partials, int Cin, int H, int W, int Cout, int Ho, int Wo, int stride, int pad, int relu,
-    int npg, int y_bf16) {
+    int npg, int y_bf16, float* red, int bx, int by) {
     constexpr int KK = K * K;
-    MEDT_STATIC_SHARED float red[MEDT_WAVES * OT * 2 * 2];
     const int HoWo = Ho * Wo, per_group = npg * HoWo, ppg = (per_group + MEDT_THREADS - 1) / MEDT_THREADS;
-    const int grp = blockIdx.x / ppg, part = blockIdx.x - grp * ppg, o0 = blockIdx.y * OT;
+    const int grp = bx / ppg, part = bx - grp * ppg, o0 = by * OT;
     const int q = part * MEDT_THREADS + threadIdx.x;
     const bool ok = q < per_group;
     const int ni = ok ? q / HoWo : 0, p = ok ? q - ni * HoWo : 0;
@@ -88,8 +88,42 @@ __global__ __launch_bounds__(MEDT_THREADS) void conv2d_fwd_kernel(
             v[2 * o] = a;
             v[2 * o + 1] = a * a;
         }
-        block_sum_d<2 * OT>(v, red, reinterpret_cast<double*>(partials) + ((size_t)blockIdx.x * Cout + o0) * 2);
+        block_sum_d<2 * OT>(v, red, reinterpret_cast<double*>(partials) + ((size_t)bx * Cout + o0) * 2);
     }
+}
+
+template <int K, int OT>
+__global__ __launch_bounds__(MEDT_THREADS) void conv2d_fwd_kernel(
+    const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ y,
+    float* __restrict__ partials, int Cin, int H, int W, int Cout, int Ho, int Wo, int stride, int pad, int relu,
+    int npg, int y_bf16) {
+    MEDT_STATIC_SHARED float red[MEDT_WAVES * OT * 2 * 2];
+    conv2d_fwd_body<K, OT>(x, w, bias, y, partials, Cin, H, W, Cout, Ho, Wo, stride, pad, relu, npg, y_bf16, red, blockIdx.x,
+                           blockIdx.y);
+}
+
+// Two independent 1x1 convolution + BatchNorm-partials problems in ONE launch (conv_down and the downsample path of a block's
+// first unit read the same x: medt_conv_block_pair_fwd).  Blocks [0, blocksA) are problem 0's grid, row-major (gx, Cout / OT), the
+// rest problem 1's: each keeps its own grid shape inside its range, and the choice is uniform over the workgroup.  Both problems
+// run the SMALLER of the two output-channel tiles the single launches would pick: a lane's accumulation order over the input
+// channels, and the order of the BatchNorm partial sums (one slot per position block and channel), do not depend on the tile, so
+// z and the partials are the bits of the single launches.
+struct ConvFwdJob {
+    const float *x, *w;
+    float *y, *partials;
+    int Cin, H, W, Cout, Ho, Wo, stride, pad, npg, gx;
+};
+struct ConvFwdPair { ConvFwdJob job[2]; int blocksA; };
+
+template <int OT>
+__global__ __launch_bounds__(MEDT_THREADS) void conv1x1_fwd_pair_kernel(ConvFwdPair p) {
+    MEDT_STATIC_SHARED float red[MEDT_WAVES * OT * 2 * 2];
+    const int second = (int)blockIdx.x >= p.blocksA ? 1 : 0;
+    const ConvFwdJob& j = p.job[second];
+    const int local = (int)blockIdx.x - (second ? p.blocksA : 0);
+    const int by = local / j.gx, bx = local - by * j.gx;
+    conv2d_fwd_body<1, OT>(j.x, j.w, nullptr, j.y, j.partials, j.Cin, j.H, j.W, j.Cout, j.Ho, j.Wo, j.stride, j.pad, 0, j.npg, 0,
+                           red, bx, by);
 }
 
 int conv2d_parts_per_group(int N, int groups, int HoWo) { return cdiv((N / groups) * HoWo, MEDT_THREADS); }
@@ -300,6 +334,49 @@ int conv2d_fwd(const float* x, const float* w, const float* bias, float* y, floa
     }
     set_error("conv2d: kernel size %d unsupported (1, 3, 7)", K);
     return MEDT_EUNSUPPORTED;
+}
+
+// true: conv2d_fwd() above runs this fp32 1x1 problem on conv2d_fwd_kernel<1, .> (the same order as its dispatch)
+bool conv1x1_fwd_plain(int N, int groups, int Cin, int H, int W, int Cout, int K, int stride, int pad) {
+    if (K != 1 || pad != 0 || stride < 1) return false;
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const long pos = (long)N * Ho * Wo;
+    if (conv_stem7_ok(Cin, H, W, Cout, K, stride, pad) || conv_use_mfma(Cin, Cout, K, stride, pos)) return false;
+    if ((conv_thin_mode() & 1) && conv_thin_ok(N, groups, Cin, H, W, Cout, K, stride, pad)) return false;
+    return !conv_fwd_ws_ok(Cin, Cout, K, stride, pos);
+}
+
+// Two conv1x1_fwd_plain() problems (no bias, no ReLU: the convolutions in front of a BatchNorm) in one launch: z and the partial
+// sums are the bits of two conv2d_fwd() calls.  partials may be NULL (eval mode).
+int conv1x1_fwd_pair(const Conv1x1Problem& a, const Conv1x1Problem& b, hipStream_t s) {
+    if (abl_skip(a.N >= 16 ? "conv1_fwd_l" : "conv1_fwd_g")) return MEDT_OK;
+    const Conv1x1Problem* in[2] = {&a, &b};
+    ConvFwdPair p;
+    int tile = 16;
+    for (int i = 0; i < 2; ++i) {
+        const Conv1x1Problem& q = *in[i];
+        ConvFwdJob& j = p.job[i];
+        j.x = q.x; j.w = q.w; j.y = q.y; j.partials = q.partials;
+        j.Cin = q.Cin; j.H = q.H; j.W = q.W; j.Cout = q.Cout; j.stride = q.stride; j.pad = 0;
+        j.Ho = (q.H - 1) / q.stride + 1; j.Wo = (q.W - 1) / q.stride + 1;
+        j.npg = q.N / q.groups;
+        j.gx = q.groups * conv2d_parts_per_group(q.N, q.groups, j.Ho * j.Wo);
+        const int t = pick_tile(q.Cout, 16, j.gx);
+        if (t < tile) tile = t;
+    }
+    while (a.Cout % tile || b.Cout % tile) tile >>= 1;
+    p.blocksA = p.job[0].gx * (a.Cout / tile);
+    const unsigned blocks = (unsigned)(p.blocksA + p.job[1].gx * (b.Cout / tile));
+#define MEDT_LAUNCH_PAIR(OT) hipLaunchKernelGGL(conv1x1_fwd_pair_kernel<OT>, dim3(blocks), dim3(MEDT_THREADS), 0, s, p)
+    switch (tile) {
+        case 16: MEDT_LAUNCH_PAIR(16); break;
+        case 8: MEDT_LAUNCH_PAIR(8); break;
+        case 4: MEDT_LAUNCH_PAIR(4); break;
+        case 2: MEDT_LAUNCH_PAIR(2); break;
+        default: MEDT_LAUNCH_PAIR(1); break;
+    }
+#undef MEDT_LAUNCH_PAIR
+    return launch_status("conv1x1_fwd_pair");
 }
 
 // --------------------------------------------------------------------------- //

@@ -75,10 +75,10 @@ static __host__ __device__ inline int conv_small_ksplit(int P, int Cin) {
     return ks;
 }
 
+// (the body takes its block coordinates as arguments: conv1x1_bn_small_fwd_pair_kernel below runs two problems in one grid)
 template <int T, int SC_NOC>                        // T = 256 ... 1024 threads (one position per thread when the group has
-__global__ __launch_bounds__(T) void conv1x1_bn_small_fwd_kernel(SmallConvArgs a) {      // 1024), SC_NOC output channels
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int grp = blockIdx.x, oc0 = blockIdx.y * SC_NOC, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__device__ __forceinline__ void conv1x1_bn_small_fwd_body(const SmallConvArgs& a, float* smem, int bx, int by) {   // 1024), SC_NOC output channels
+    const int grp = bx, oc0 = by * SC_NOC, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int NW = T >> 6;
     const int Cin = a.Cin, W = a.W, HW = a.H * a.W, st = a.stride, Ho = a.H / st, Wo = a.W / st, HoWo = Ho * Wo;
     const int P = a.npg * HoWo, n0 = grp * a.npg;
@@ -245,6 +245,24 @@ __global__ __launch_bounds__(T) void conv1x1_bn_small_fwd_kernel(SmallConvArgs a
     }
 }
 
+template <int T, int SC_NOC>
+__global__ __launch_bounds__(T) void conv1x1_bn_small_fwd_kernel(SmallConvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    conv1x1_bn_small_fwd_body<T, SC_NOC>(a, smem, blockIdx.x, blockIdx.y);
+}
+
+// Two problems of the SAME instantiation (block size, channel tile) in one launch: blocks [0, blocksA) are problem 0's grid, row-major
+// (groups, Cout / SC_NOC), the rest problem 1's; the choice is uniform over the workgroup.  Dynamic LDS: the larger of the two.
+struct SmallConvPair { SmallConvArgs job[2]; int gx[2]; int blocksA; };
+template <int T, int SC_NOC>
+__global__ __launch_bounds__(T) void conv1x1_bn_small_fwd_pair_kernel(SmallConvPair p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int second = (int)blockIdx.x >= p.blocksA ? 1 : 0;
+    const int local = (int)blockIdx.x - (second ? p.blocksA : 0), gx = p.gx[second];
+    const int by = local / gx;
+    conv1x1_bn_small_fwd_body<T, SC_NOC>(p.job[second], smem, local - by * gx, by);
+}
+
 static size_t conv_small_lds(int P, int Cin, int noc) {
     const int ks = conv_small_ksplit(P, Cin);
     return ((size_t)noc * P + (size_t)Cin * noc + 8 * noc + (ks > 1 ? (size_t)ks * noc * P : 0)) * sizeof(float);
@@ -281,14 +299,53 @@ bool conv_small_ok(const medt_conv_desc& d) {
     return true;
 }
 
-int conv_small_fwd(const medt_conv_desc& d, const float* x, const float* w, const medt_bn_ptrs& bn, const float* res,
-                   float* z, float* y, float* partials, hipStream_t s) {
-    if (abl_skip("conv_small_fwd")) return MEDT_OK;
+static SmallConvArgs conv_small_args(const medt_conv_desc& d, const float* x, const float* w, const medt_bn_ptrs& bn, const float* res,
+                                     float* z, float* y, float* partials) {
     SmallConvArgs a;
     a.x = x; a.w = w; a.res = d.has_res ? res : nullptr; a.bn = bn; a.z = z; a.y = y; a.partials = partials;
     a.N = d.N; a.Cin = d.Cin; a.H = d.H; a.W = d.W; a.Cout = d.Cout; a.stride = d.stride; a.npg = d.N / d.bn_groups;
     a.relu = d.relu; a.training = d.training ? 1 : 0; a.eps = d.eps;
-    const int P = a.npg * (d.H / d.stride) * (d.W / d.stride);
+    return a;
+}
+static int conv_small_positions(const medt_conv_desc& d) { return (d.N / d.bn_groups) * (d.H / d.stride) * (d.W / d.stride); }
+
+// both conv_small_ok(): may the two run as one launch?  (the same kernel instantiation: block size and channel tile)
+bool conv_small_pair_ok(const medt_conv_desc& a, const medt_conv_desc& b) {
+    const int Pa = conv_small_positions(a), Pb = conv_small_positions(b);
+    return conv_small_threads(Pa) == conv_small_threads(Pb) && conv_small_noc(Pa, a.Cin) == conv_small_noc(Pb, b.Cin);
+}
+
+int conv_small_fwd_pair(const medt_conv_desc& da, const float* xa, const float* wa, const medt_bn_ptrs& bna, const float* resa,
+                        float* za, float* ya, float* partialsa, const medt_conv_desc& db, const float* xb, const float* wb,
+                        const medt_bn_ptrs& bnb, const float* resb, float* zb, float* yb, float* partialsb, hipStream_t s) {
+    if (abl_skip("conv_small_fwd")) return MEDT_OK;
+    SmallConvPair p;
+    p.job[0] = conv_small_args(da, xa, wa, bna, resa, za, ya, partialsa);
+    p.job[1] = conv_small_args(db, xb, wb, bnb, resb, zb, yb, partialsb);
+    const int Pa = conv_small_positions(da), Pb = conv_small_positions(db);
+    const int threads = conv_small_threads(Pa), noc = conv_small_noc(Pa, da.Cin);
+    p.gx[0] = da.bn_groups;
+    p.gx[1] = db.bn_groups;
+    p.blocksA = da.bn_groups * (da.Cout / noc);
+    const dim3 grid((unsigned)(p.blocksA + db.bn_groups * (db.Cout / noc)));
+    const size_t la = conv_small_lds(Pa, da.Cin, noc), lb = conv_small_lds(Pb, db.Cin, noc), lds = la > lb ? la : lb;
+#define MEDT_SMALL_PAIR(TT)                                                                                   \
+    do {                                                                                                      \
+        if (noc == 16) hipLaunchKernelGGL((conv1x1_bn_small_fwd_pair_kernel<TT, 16>), grid, dim3(TT), lds, s, p); \
+        else hipLaunchKernelGGL((conv1x1_bn_small_fwd_pair_kernel<TT, 8>), grid, dim3(TT), lds, s, p);         \
+    } while (0)
+    if (threads == 256) MEDT_SMALL_PAIR(256);
+    else if (threads == 512) MEDT_SMALL_PAIR(512);
+    else MEDT_SMALL_PAIR(1024);
+#undef MEDT_SMALL_PAIR
+    return launch_status("conv1x1_bn_small_fwd_pair");
+}
+
+int conv_small_fwd(const medt_conv_desc& d, const float* x, const float* w, const medt_bn_ptrs& bn, const float* res,
+                   float* z, float* y, float* partials, hipStream_t s) {
+    if (abl_skip("conv_small_fwd")) return MEDT_OK;
+    const SmallConvArgs a = conv_small_args(d, x, w, bn, res, z, y, partials);
+    const int P = conv_small_positions(d);
     const int threads = conv_small_threads(P);
     const int noc = conv_small_noc(P, d.Cin);
     const dim3 grid(d.bn_groups, d.Cout / noc);

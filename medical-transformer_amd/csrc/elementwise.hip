@@ -53,9 +53,9 @@ struct BnFinApplyArgs {
     float eps;
 };
 constexpr int BFA_PER_THREAD = 16;
-__global__ __launch_bounds__(MEDT_THREADS) void bn_fin_apply_kernel(BnFinApplyArgs a) {
-    MEDT_STATIC_SHARED double redd[2 * MEDT_WAVES];
-    const int grp = blockIdx.x / a.parts, part = blockIdx.x - grp * a.parts, c = blockIdx.y, tid = threadIdx.x;
+// (the body takes its block coordinates as arguments: bn_fin_apply_pair_kernel below runs two problems in one grid)
+__device__ __forceinline__ void bn_fin_apply_body(const BnFinApplyArgs& a, double* redd, int bx, int by) {
+    const int grp = bx / a.parts, part = bx - grp * a.parts, c = by, tid = threadIdx.x;
     const int gc = grp * a.C + c;
     const float gam = a.weight[c], bet = a.bias[c];
     float mean_f, rstd_f, scale, shift;
@@ -127,16 +127,53 @@ __global__ __launch_bounds__(MEDT_THREADS) void bn_fin_apply_kernel(BnFinApplyAr
     }
 }
 
-int bn_fin_apply(const float* z, const float* partials, int ppg, double count, const medt_bn_ptrs& bn, float eps, int training,
-                 BnStats st, const float* res, float* y, int N, int C, int HW, int groups, int relu, hipStream_t s) {
+__global__ __launch_bounds__(MEDT_THREADS) void bn_fin_apply_kernel(BnFinApplyArgs a) {
+    MEDT_STATIC_SHARED double redd[2 * MEDT_WAVES];
+    bn_fin_apply_body(a, redd, blockIdx.x, blockIdx.y);
+}
+
+// Two bn_fin_apply problems in one launch, as a two-entry job table: blocks [0, blocksA) are problem 0's grid, row-major
+// (groups * parts, C), the rest problem 1's -- each keeps its own grid shape inside its range; the choice is uniform over the workgroup
+struct BnFinApplyPair { BnFinApplyArgs job[2]; int gx[2]; int blocksA; };
+__global__ __launch_bounds__(MEDT_THREADS) void bn_fin_apply_pair_kernel(BnFinApplyPair p) {
+    MEDT_STATIC_SHARED double redd[2 * MEDT_WAVES];
+    const int second = (int)blockIdx.x >= p.blocksA ? 1 : 0;
+    const int local = (int)blockIdx.x - (second ? p.blocksA : 0), gx = p.gx[second];
+    const int by = local / gx;
+    bn_fin_apply_body(p.job[second], redd, local - by * gx, by);
+}
+
+static BnFinApplyArgs bn_fin_apply_args(const float* z, const float* partials, int ppg, double count, const medt_bn_ptrs& bn, float eps,
+                                        int training, BnStats st, const float* res, float* y, int N, int C, int HW, int groups,
+                                        int relu) {
     BnFinApplyArgs a;
     a.z = z; a.partials = partials; a.weight = bn.weight; a.bias = bn.bias; a.running_mean = bn.running_mean;
     a.running_var = bn.running_var; a.res = res; a.y = y; a.st = st; a.C = C; a.HW = HW; a.npg = N / groups; a.ppg = ppg;
     a.parts = cdiv(a.npg * HW, MEDT_THREADS * BFA_PER_THREAD); a.relu = relu; a.training = training; a.count = count;
     a.vec4 = ((HW & 3) == 0 && (((uintptr_t)z | (uintptr_t)y | (uintptr_t)res) & 15) == 0) ? 1 : 0;
     a.eps = eps;
+    return a;
+}
+
+int bn_fin_apply(const float* z, const float* partials, int ppg, double count, const medt_bn_ptrs& bn, float eps, int training,
+                 BnStats st, const float* res, float* y, int N, int C, int HW, int groups, int relu, hipStream_t s) {
+    const BnFinApplyArgs a = bn_fin_apply_args(z, partials, ppg, count, bn, eps, training, st, res, y, N, C, HW, groups, relu);
     hipLaunchKernelGGL(bn_fin_apply_kernel, dim3(groups * a.parts, C), dim3(MEDT_THREADS), 0, s, a);
     return launch_status("bn_fin_apply");
+}
+
+int bn_fin_apply_pair(const BnFinApplyProblem& a, const BnFinApplyProblem& b, hipStream_t s) {
+    const BnFinApplyProblem* in[2] = {&a, &b};
+    BnFinApplyPair p;
+    for (int i = 0; i < 2; ++i) {
+        const BnFinApplyProblem& q = *in[i];
+        p.job[i] = bn_fin_apply_args(q.z, q.partials, q.ppg, q.count, *q.bn, q.eps, q.training, q.st, q.res, q.y, q.N, q.C, q.HW,
+                                     q.groups, q.relu);
+        p.gx[i] = q.groups * p.job[i].parts;
+    }
+    p.blocksA = p.gx[0] * a.C;
+    hipLaunchKernelGGL(bn_fin_apply_pair_kernel, dim3((unsigned)(p.blocksA + p.gx[1] * b.C)), dim3(MEDT_THREADS), 0, s, p);
+    return launch_status("bn_fin_apply_pair");
 }
 
 // g = dy * (y > 0 if relu) ; partials[group][part][C][2] = [sum g, sum g*zhat]     grid (groups*ppg, C),

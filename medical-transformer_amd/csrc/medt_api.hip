@@ -576,62 +576,154 @@ size_t medt_conv_workspace_bytes(const medt_conv_desc* d) {
     return align_up(c.off, 256) + 256;
 }
 
-int medt_conv_block_fwd(const medt_conv_desc* d, const float* x, const float* w, const float* bias,
-                        const medt_bn_ptrs* bn, const float* res, float* z, float* y, float* stats, void* ws,
-                        size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace medt {
+// One medt_conv_block_fwd call: its arguments, the checks every entry point that takes them shares, and its stages.
+struct ConvFwdCall {
+    const medt_conv_desc* d;
+    const float *x, *w, *bias;
+    const medt_bn_ptrs* bn;
+    const float* res;
+    float *z, *y, *stats;
+    void* ws;
+    size_t ws_bytes;
     ConvGeom g;
-    int rc = conv_geom(d, &g);
+    float *partials, *ksplit_fwd;       // carved from the workspace by check()
+    int tr;
+    double count;                       // values per (BatchNorm group, channel)
+
+    int check() {
+        int rc = conv_geom(d, &g);
+        if (rc) return rc;
+        if (!x || !w || !y || (d->has_bias && !bias) || (d->has_bn && (!bn || !z || !stats)) || (d->has_res && !res)) {
+            set_error("conv fwd: null pointer"); return MEDT_EINVAL;
+        }
+        Carver c(ws, ws_bytes);
+        ConvWs cw(c, d, g);
+        if (!ws || !c.ok()) { set_error("conv workspace too small: need %zu", c.off); return MEDT_EWORKSPACE; }
+        partials = cw.partials;
+        ksplit_fwd = cw.ksplit_fwd;
+        tr = d->training ? 1 : 0;
+        count = d->has_bn ? (double)(d->N / d->bn_groups) * g.HoWo : 0.0;
+        return MEDT_OK;
+    }
+    // what a BatchNorm block's forward needs on top of check()
+    int check_bn() const {
+        if (!tr && (!bn->running_mean || !bn->running_var)) { set_error("conv fwd: eval mode needs running statistics"); return MEDT_EINVAL; }
+        if (tr && count <= 1.0) {
+            set_error("conv fwd: training-mode BatchNorm needs more than 1 value per channel"); return MEDT_EINVAL;
+        }
+        return MEDT_OK;
+    }
+    BnStats st() const { return BnStats(stats, d->bn_groups * d->Cout); }
+    // the flipped weights a training-mode 3x3 forward leaves behind the statistics (see medt_conv_stats_floats)
+    int preflip(hipStream_t s) const;
+    // after the fused small kernel: the saved statistics and the ordered running-stat updates
+    int finish_small(hipStream_t s) const {
+        if (Queue* q = queue_for(s)) {
+            q->fin.push_back(FinJob{make_fin(partials, 1, d->Cout, count, *bn, st()), d->bn_groups, tr, d->momentum, d->eps});
+            return MEDT_OK;
+        }
+        return bn_finalize(partials, 1, d->bn_groups, d->Cout, count, *bn, d->momentum, d->eps, tr, st(), s);
+    }
+    // after convolution + bn_fin_apply: the running statistics follow off the layer chain
+    int finish_generic(hipStream_t s) const {
+        if (!tr) return MEDT_OK;
+        if (Queue* q = queue_for(s)) {
+            q->fin.push_back(FinJob{make_fin(partials, g.ppg, d->Cout, count, *bn, st()), d->bn_groups, 2, d->momentum, d->eps});
+            return MEDT_OK;
+        }
+        return bn_finalize(partials, g.ppg, d->bn_groups, d->Cout, count, *bn, d->momentum, d->eps, 2, st(), s);
+    }
+    BnFinApplyProblem apply_problem() const {
+        return BnFinApplyProblem{z, partials, d->has_res ? res : nullptr, bn, y, st(), g.ppg, d->N, d->Cout, g.HoWo, d->bn_groups,
+                                 d->relu, tr, count, d->eps};
+    }
+    int run(hipStream_t s) const;
+};
+}  // namespace medt
+
+extern "C" {
+
+int medt::ConvFwdCall::preflip(hipStream_t s) const {
+    if (!(stats && conv_preflip(d))) return MEDT_OK;       // (nothing in the forward chain reads it)
+    float* wt = conv_preflip_ptr(d, stats);
+    if (Queue* q = queue_for(s)) { q->flip.push_back(FlipJob{w, wt, d->Cout, d->Cin, d->K}); return MEDT_OK; }
+    return conv_flip_weights(w, wt, d->Cout, d->Cin, d->K, s);
+}
+
+int medt::ConvFwdCall::run(hipStream_t s) const {
+    int rc = preflip(s);
     if (rc) return rc;
-    if (!x || !w || !y || (d->has_bias && !bias) || (d->has_bn && (!bn || !z || !stats)) || (d->has_res && !res)) {
-        set_error("conv fwd: null pointer"); return MEDT_EINVAL;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    Carver c(ws, ws_bytes);
-    ConvWs cw(c, d, g);
-    if (!ws || !c.ok()) { set_error("conv workspace too small: need %zu", c.off); return MEDT_EWORKSPACE; }
-    if (stats && conv_preflip(d)) {            // (see medt_conv_stats_floats; nothing in the forward chain reads it)
-        float* wt = conv_preflip_ptr(d, stats);
-        if (Queue* q = queue_for(s)) q->flip.push_back(FlipJob{w, wt, d->Cout, d->Cin, d->K});
-        else if ((rc = conv_flip_weights(w, wt, d->Cout, d->Cin, d->K, s))) return rc;
-    }
     if (!d->has_bn)
-        return conv2d_fwd(x, w, d->has_bias ? bias : nullptr, y, nullptr, cw.ksplit_fwd, d->N, d->Cin, d->H, d->W, d->Cout,
+        return conv2d_fwd(x, w, d->has_bias ? bias : nullptr, y, nullptr, ksplit_fwd, d->N, d->Cin, d->H, d->W, d->Cout,
                           d->K, d->stride, d->pad, d->relu, 1, s);
-    const int tr = d->training ? 1 : 0;
-    if (!tr && (!bn->running_mean || !bn->running_var)) { set_error("conv fwd: eval mode needs running statistics"); return MEDT_EINVAL; }
-    if (tr && (double)(d->N / d->bn_groups) * g.HoWo <= 1.0) {
-        set_error("conv fwd: training-mode BatchNorm needs more than 1 value per channel"); return MEDT_EINVAL;
-    }
-    BnStats st(stats, d->bn_groups * d->Cout);
+    if ((rc = check_bn())) return rc;
     if (conv_small_ok(*d)) {
         // small BN groups (local branch): conv + exact block-level statistics + normalise/residual/ReLU in one kernel,
         // then the saved statistics and the ordered running-stat updates
-        if ((rc = conv_small_fwd(*d, x, w, *bn, res, z, y, cw.partials, s))) return rc;
-        if (Queue* q = queue_for(s)) {
-            q->fin.push_back(FinJob{make_fin(cw.partials, 1, d->Cout, (double)(d->N / d->bn_groups) * g.HoWo, *bn, st),
-                                    d->bn_groups, tr, d->momentum, d->eps});
-            return MEDT_OK;
-        }
-        return bn_finalize(cw.partials, 1, d->bn_groups, d->Cout, (double)(d->N / d->bn_groups) * g.HoWo, *bn, d->momentum,
-                           d->eps, tr, st, s);
+        if ((rc = conv_small_fwd(*d, x, w, *bn, res, z, y, partials, s))) return rc;
+        return finish_small(s);
     }
-    if ((rc = conv2d_fwd(x, w, nullptr, z, tr ? cw.partials : nullptr, cw.ksplit_fwd, d->N, d->Cin, d->H, d->W, d->Cout, d->K,
+    if ((rc = conv2d_fwd(x, w, nullptr, z, tr ? partials : nullptr, ksplit_fwd, d->N, d->Cin, d->H, d->W, d->Cout, d->K,
                          d->stride, d->pad, 0, d->bn_groups, s))) return rc;
     static const bool fused_fin = true;
-    const double count = (double)(d->N / d->bn_groups) * g.HoWo;
     if (!fused_fin) {
-        if ((rc = bn_finalize(cw.partials, g.ppg, d->bn_groups, d->Cout, count, *bn, d->momentum, d->eps, tr, st, s))) return rc;
-        return bn_apply_act(z, st, d->has_res ? res : nullptr, y, d->N, d->Cout, g.HoWo, d->bn_groups, d->relu, s);
+        if ((rc = bn_finalize(partials, g.ppg, d->bn_groups, d->Cout, count, *bn, d->momentum, d->eps, tr, st(), s))) return rc;
+        return bn_apply_act(z, st(), d->has_res ? res : nullptr, y, d->N, d->Cout, g.HoWo, d->bn_groups, d->relu, s);
     }
     // statistics + normalise / residual / ReLU in one launch; the running statistics follow off the layer chain
-    if ((rc = bn_fin_apply(z, cw.partials, g.ppg, count, *bn, d->eps, tr, st, d->has_res ? res : nullptr, y, d->N, d->Cout,
+    if ((rc = bn_fin_apply(z, partials, g.ppg, count, *bn, d->eps, tr, st(), d->has_res ? res : nullptr, y, d->N, d->Cout,
                            g.HoWo, d->bn_groups, d->relu, s))) return rc;
-    if (!tr) return MEDT_OK;
-    if (Queue* q = queue_for(s)) {
-        q->fin.push_back(FinJob{make_fin(cw.partials, g.ppg, d->Cout, count, *bn, st), d->bn_groups, 2, d->momentum, d->eps});
-        return MEDT_OK;
+    return finish_generic(s);
+}
+
+int medt_conv_block_fwd(const medt_conv_desc* d, const float* x, const float* w, const float* bias,
+                        const medt_bn_ptrs* bn, const float* res, float* z, float* y, float* stats, void* ws,
+                        size_t ws_bytes, void* stream) {
+    ConvFwdCall c{d, x, w, bias, bn, res, z, y, stats, ws, ws_bytes};
+    int rc = c.check();
+    if (rc) return rc;
+    return c.run((hipStream_t)stream);
+}
+
+// Two independent blocks in side-by-side launches (see medt_abi.h).  The plan of each member is that of its single call; the
+// members share launches stage by stage where both take the same kernel family:
+//   both the fused small kernel (same instantiation)    -> one launch
+//   both conv2d_fwd_kernel<1, .> + bn_fin_apply         -> convolution || convolution, then apply || apply
+// anything else (mixed families, 3x3, no BatchNorm): the two single plans, A then B.  Recorded jobs: A's, then B's, as from two calls.
+int medt_conv_block_pair_fwd(const medt_conv_desc* da, const float* xa, const float* wa, const float* biasa,
+                             const medt_bn_ptrs* bna, const float* resa, float* za, float* ya, float* statsa, void* wsa,
+                             size_t wsa_bytes, const medt_conv_desc* db, const float* xb, const float* wb, const float* biasb,
+                             const medt_bn_ptrs* bnb, const float* resb, float* zb, float* yb, float* statsb, void* wsb,
+                             size_t wsb_bytes, void* stream) {
+    ConvFwdCall a{da, xa, wa, biasa, bna, resa, za, ya, statsa, wsa, wsa_bytes};
+    ConvFwdCall b{db, xb, wb, biasb, bnb, resb, zb, yb, statsb, wsb, wsb_bytes};
+    int rc;
+    if ((rc = a.check()) || (rc = b.check())) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const bool bn1x1 = da->has_bn && db->has_bn && da->K == 1 && db->K == 1 && da->N == db->N;
+    if (bn1x1 && conv_small_ok(*da) && conv_small_ok(*db) && conv_small_pair_ok(*da, *db)) {
+        if ((rc = a.check_bn()) || (rc = b.check_bn())) return rc;
+        if ((rc = conv_small_fwd_pair(*da, xa, wa, *bna, resa, za, ya, a.partials, *db, xb, wb, *bnb, resb, zb, yb, b.partials, s)))
+            return rc;
+        if ((rc = a.finish_small(s))) return rc;
+        return b.finish_small(s);
     }
-    return bn_finalize(cw.partials, g.ppg, d->bn_groups, d->Cout, count, *bn, d->momentum, d->eps, 2, st, s);
+    if (bn1x1 && !conv_small_ok(*da) && !conv_small_ok(*db) &&
+        conv1x1_fwd_plain(da->N, da->bn_groups, da->Cin, da->H, da->W, da->Cout, da->K, da->stride, da->pad) &&
+        conv1x1_fwd_plain(db->N, db->bn_groups, db->Cin, db->H, db->W, db->Cout, db->K, db->stride, db->pad)) {
+        if ((rc = a.check_bn()) || (rc = b.check_bn())) return rc;
+        const Conv1x1Problem pa{xa, wa, za, a.tr ? a.partials : nullptr, da->N, da->Cin, da->H, da->W, da->Cout, da->stride, da->bn_groups};
+        const Conv1x1Problem pb{xb, wb, zb, b.tr ? b.partials : nullptr, db->N, db->Cin, db->H, db->W, db->Cout, db->stride, db->bn_groups};
+        if ((rc = conv1x1_fwd_pair(pa, pb, s))) return rc;
+        if ((rc = bn_fin_apply_pair(a.apply_problem(), b.apply_problem(), s))) return rc;
+        if ((rc = a.finish_generic(s))) return rc;
+        return b.finish_generic(s);
+    }
+    if ((rc = a.run(s))) return rc;
+    return b.run(s);
 }
 
 int medt_conv_block_bwd(const medt_conv_desc* d, const float* x, const float* w, const medt_bn_ptrs* bn, const float* z,

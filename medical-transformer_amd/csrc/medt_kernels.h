@@ -256,6 +256,29 @@ int bn_act_bwd_small(const medt_conv_desc& d, const float* dy, const float* y, c
 int bn_fin_apply(const float* z, const float* partials, int ppg, double count, const medt_bn_ptrs& bn, float eps, int training,
                  BnStats st, const float* res, float* y, int N, int C, int HW, int groups, int relu, hipStream_t s);
 bool conv_fwd_ws_ok(int Cin, int Cout, int K, int stride, long positions);      // conv.hip: wave-split forward (64-position parts)
+// Two-problem launches (medt_conv_block_pair_fwd: conv_down and the downsample path of a block's first unit, which read the same x):
+// each writes the bits of the two single launches it stands for
+struct BnFinApplyProblem {          // the arguments of one bn_fin_apply() call
+    const float *z, *partials, *res;
+    const medt_bn_ptrs* bn;
+    float* y;
+    BnStats st;
+    int ppg, N, C, HW, groups, relu, training;
+    double count;
+    float eps;
+};
+int bn_fin_apply_pair(const BnFinApplyProblem& a, const BnFinApplyProblem& b, hipStream_t s);
+struct Conv1x1Problem {             // a 1x1 convolution in front of a BatchNorm: no bias, no ReLU; partials may be NULL (eval mode)
+    const float *x, *w;
+    float *y, *partials;
+    int N, Cin, H, W, Cout, stride, groups;
+};
+bool conv1x1_fwd_plain(int N, int groups, int Cin, int H, int W, int Cout, int K, int stride, int pad);   // conv.hip: conv2d_fwd_kernel<1, .>
+int conv1x1_fwd_pair(const Conv1x1Problem& a, const Conv1x1Problem& b, hipStream_t s);
+bool conv_small_pair_ok(const medt_conv_desc& a, const medt_conv_desc& b);       // conv_small.hip: same block size and channel tile
+int conv_small_fwd_pair(const medt_conv_desc& da, const float* xa, const float* wa, const medt_bn_ptrs& bna, const float* resa,
+                        float* za, float* ya, float* partialsa, const medt_conv_desc& db, const float* xb, const float* wb,
+                        const medt_bn_ptrs& bnb, const float* resb, float* zb, float* yb, float* partialsb, hipStream_t s);
 int bn_chan_threads(const medt_conv_desc& d, int HoWo);       // conv_small.hip: one workgroup per (group, channel); 0 = no
 int bn_act_bwd_chan(const medt_conv_desc& d, const float* dy, const float* y, const float* z, BnStats st,
                     const float* weight, float* g, float* dz, float* partials, int HoWo, hipStream_t s);

@@ -27,6 +27,7 @@ GRID = 4
 TWO_STREAMS = os.environ.get("MEDT_TWO_STREAMS", "1") != "0"
 SINKS = os.environ.get("MEDT_GRAD_SINKS", "1") != "0"       # gradient fan-in in dgrad epilogues (ops.GradSink)
 EARLY_FIN = os.environ.get("MEDT_EARLY_FIN", "1") != "0"    # forward bookkeeping flushed per branch, off the loss trunk
+PAIR = os.environ.get("MEDT_PAIR", "1") != "0"              # conv_down and the downsample path of a first block: side-by-side launches
 _side = {}
 
 
@@ -68,6 +69,12 @@ def axial_block_forward(blk, x, bn_groups: int = 1):
     if pre is None:
         pre = {"down": None, "h": None, "w": None, "up": None}
     pre.setdefault("ds", None)
+    if PAIR and blk.downsample is not None and pre["down"] is None and pre["ds"] is None:
+        # conv_down and the downsample path read the same x and do not depend on each other: their kernels share launches
+        # (ops.conv_block_pair_pre); the two conv_block calls below adopt the results as they adopt block.py's
+        both = ops.conv_block_pair_pre(x, blk.conv_down, blk.bn1, True, blk.downsample[0], blk.downsample[1], False, bn_groups)
+        if both is not None:
+            pre["down"], pre["ds"] = both
     out = ops.conv_block(x, blk.conv_down, blk.bn1, relu=True, training=blk.bn1.training, bn_groups=bn_groups,
                          x_sink=sink, x_role="final", pre=pre["down"])
     out = blk.hight_block.run(out, bn_groups, False, pre["h"])

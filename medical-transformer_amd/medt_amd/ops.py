@@ -212,6 +212,50 @@ def conv_block(x, conv, bn=None, res=None, relu=False, training=False, bn_groups
                              bn.bias if bn is not None else None, res, cfg, training)
 
 
+PAIR_CALLS = 0      # medt_conv_block_pair_fwd calls issued by this process (tests assert that the pair path is reached)
+
+
+def conv_block_pair_pre(x, conv_a, bn_a, relu_a, conv_b, bn_b, relu_b, bn_groups=1):
+    """The forwards of two 1x1 conv + BatchNorm blocks that read the same x (a first block's conv_down and its downsample
+    path) in side-by-side launches (medt_conv_block_pair_fwd).  Returns ((z, y, stats) of a, (z, y, stats) of b): the two
+    conv_block calls adopt them through `pre`, so the autograd graph and everything saved are those of two single calls.
+    None when the pair does not apply (not both 1x1 with BatchNorm, or a residual input)."""
+    global PAIR_CALLS
+    if bn_a is None or bn_b is None or conv_a.bias is not None or conv_b.bias is not None:
+        return None
+    if conv_a.weight.shape[2] != 1 or conv_b.weight.shape[2] != 1:
+        return None
+    _require_device(x)
+    lib = L.lib()
+    x = x.contiguous()
+    N, _, H, W = x.shape
+    dev = x.device
+    args, outs, held = [], [], []
+    for conv, bn, relu in ((conv_a, bn_a, relu_a), (conv_b, bn_b, relu_b)):
+        cfg = ConvBlockCfg(conv.stride[0], conv.padding[0], bn, relu, bn_groups)
+        w = conv.weight
+        desc = _conv_desc(x, w, cfg, False, False, bn.training)
+        s, p = cfg.stride, cfg.pad
+        y = torch.empty((N, w.shape[0], (H + 2 * p - 1) // s + 1, (W + 2 * p - 1) // s + 1), device=dev, dtype=torch.float32)
+        z = torch.empty_like(y)
+        stats = torch.empty((max(lib.medt_conv_stats_floats(C.byref(desc)), 1),), device=dev, dtype=torch.float32)
+        ws_bytes = lib.medt_conv_workspace_bytes(C.byref(desc))
+        if ws_bytes == 0:
+            raise L.MedtError("conv block pair: " + lib.medt_last_error().decode())
+        ws = torch.empty((ws_bytes,), device=dev, dtype=torch.uint8)
+        bnp = _bn_ptrs(bn, bn.training)
+        held += [desc, bnp, ws, stats]
+        args += [C.byref(desc), x.data_ptr(), w.data_ptr(), None, C.byref(bnp), None, z.data_ptr(), y.data_ptr(),
+                 stats.data_ptr(), ws.data_ptr(), ws_bytes]
+        outs.append((z, y, stats))
+    q = DEFER.recording()          # (the recorded BatchNorm finalisations write into stats at the flush)
+    L.check(lib.medt_conv_block_pair_fwd(*args, _stream()), "medt_conv_block_pair_fwd")
+    PAIR_CALLS += 1
+    if q is not None:
+        q.hold(*(t for t in held if isinstance(t, torch.Tensor)))
+    return outs[0], outs[1]
+
+
 # --------------------------------------------------------------------------- #
 # y = relu(bilinear_x2(x)) + skip
 # --------------------------------------------------------------------------- #
