@@ -564,28 +564,38 @@ __global__ __launch_bounds__(MEDT_THREADS) void attn_bwd_kernel(
     for (int c = 0; c < HQ; ++c) aq_hi[c] = aq_lo[c] = ak_hi[c] = ak_lo[c] = 0.f;
 #pragma unroll
     for (int c = 0; c < GP; ++c) av_hi[c] = av_lo[c] = 0.f;
-    if (active) {
-        const float* qp = S.reg + ls * S.RS;
-        const float* kp = qp + HQ * L;
-        const float* vp = qp + GP * L;
-        const float* g2 = S.g2 + ls * S.R2;
-        const float* lsep = S.g3 + ls * S.R3 + GP * L;
-        const float* delp = lsep + L;
-        // ---------------- row-oriented: thread owns query row i = idx ----------------
-        // (only when the wrapped-diagonal sweep below cannot run: it produces dq and the gate gradients as well)
-        if (!diag) {
-            const int i = idx;
-            float q[HQ], dsv[GP], dse[GP], dq[HQ];
+    const int lsc = active ? ls : 0;                    // (threads beyond the tile's sequences read nothing through these)
+    const float* qp = S.reg + lsc * S.RS;
+    const float* kp = qp + HQ * L;
+    const float* vp = qp + GP * L;
+    const float* g2 = S.g2 + lsc * S.R2;
+    const float* lsep = S.g3 + lsc * S.R3 + GP * L;
+    const float* delp = lsep + L;
+    // ---------------- row-oriented: thread owns query row i = idx ----------------
+    // (only when the wrapped-diagonal sweep below cannot run: it produces dq and the gate gradients as well)
+    // The relative-table gradients of this form were LDS float atomics, summed in whatever order the waves arrived: a replayed step of
+    // a network with such lengths (96 px: L = 48, 24, 12, 6) was not the eager step.  Now the whole workgroup walks j in lockstep and
+    // the tile's sequences add their terms in turn with plain read-modify-writes: at one j the rows of a sequence hit distinct
+    // entries d = i - j + L - 1, so every entry receives its terms in the fixed order (j, sequence) -- the same bits on every run.
+    if (!diag) {
+        const int i = idx;
+        float q[HQ], dsv[GP], dse[GP], dq[HQ];
 #pragma unroll
-            for (int c = 0; c < HQ; ++c) { q[c] = qp[c * L + i]; dq[c] = 0.f; }
+        for (int c = 0; c < HQ; ++c) { q[c] = active ? qp[c * L + i] : 0.f; dq[c] = 0.f; }
 #pragma unroll
-            for (int c = 0; c < GP; ++c) {
-                dsv[c] = g2[(POS ? 2 * c : c) * L + i];
-                dse[c] = POS ? g2[(2 * c + 1) * L + i] : 0.f;
-            }
-            const float lse_i = lsep[i], delta = delp[i];
-            for (int j = 0; j < L; ++j) {
-                const int d = i - j + L - 1;
+        for (int c = 0; c < GP; ++c) {
+            dsv[c] = active ? g2[(POS ? 2 * c : c) * L + i] : 0.f;
+            dse[c] = (POS && active) ? g2[(2 * c + 1) * L + i] : 0.f;
+        }
+        const float lse_i = active ? lsep[i] : 0.f, delta = active ? delp[i] : 0.f;
+        for (int j = 0; j < L; ++j) {
+            const int d = i - j + L - 1;
+            float cq[HQ], ck[HQ], cv[GP];               // this pair's terms of dtq | dtk | dtv at entry d (POS)
+#pragma unroll
+            for (int c = 0; c < HQ; ++c) cq[c] = ck[c] = 0.f;
+#pragma unroll
+            for (int c = 0; c < GP; ++c) cv[c] = 0.f;
+            if (active) {
                 float tqk = 0.f, rq = 0.f, rk = 0.f;
 #pragma unroll
                 for (int c = 0; c < HQ; ++c) {
@@ -620,23 +630,35 @@ __global__ __launch_bounds__(MEDT_THREADS) void attn_bwd_kernel(
                     for (int c = 0; c < HQ; ++c) {
                         const float kc = kp[c * L + j];
                         dq[c] = fmaf(dSqk, kc, fmaf(gq, S.tq[c * TL + d], dq[c]));
-                        if (!diag) {
-                            atomicAdd(&S.dtq[c * TL + d], gq * q[c]);
-                            atomicAdd(&S.dtk[c * TL + d], gk * kc);
-                        }
+                        cq[c] = gq * q[c];
+                        ck[c] = gk * kc;
                     }
-                    if (!diag) {
 #pragma unroll
-                        for (int c = 0; c < GP; ++c) atomicAdd(&S.dtv[c * TL + d], gv * dse[c]);
-                    }
+                    for (int c = 0; c < GP; ++c) cv[c] = gv * dse[c];
                 } else {
 #pragma unroll
                     for (int c = 0; c < HQ; ++c) dq[c] = fmaf(dSqk, kp[c * L + j], dq[c]);
                 }
             }
+            if (POS) {
+                for (int sq = 0; sq < t.nseq; ++sq) {       // (t.nseq and L are the same for every thread: the barriers are uniform)
+                    if (active && ls == sq) {
 #pragma unroll
-            for (int c = 0; c < HQ; ++c) dqkv_v[c] = dq[c];
+                        for (int c = 0; c < HQ; ++c) {
+                            S.dtq[c * TL + d] += cq[c];
+                            S.dtk[c * TL + d] += ck[c];
+                        }
+#pragma unroll
+                        for (int c = 0; c < GP; ++c) S.dtv[c * TL + d] += cv[c];
+                    }
+                    __syncthreads();
+                }
+            }
         }
+#pragma unroll
+        for (int c = 0; c < HQ; ++c) dqkv_v[c] = dq[c];
+    }
+    if (active) {
         // ---------------- wrapped diagonals: lane delta visits (i, j = (i - delta) mod L) ----------------
         // All pairs a lane visits share one of two table entries (d = delta+L-1 while i >= delta, delta-1
         // after the wrap), so the relative-table gradients accumulate in lane-private registers; the dk/dv
@@ -777,7 +799,7 @@ __global__ __launch_bounds__(MEDT_THREADS) void attn_bwd_kernel(
             for (int c = 0; c < GP; ++c) dqkv_v[GP + c] = dv[c];
         }
     }
-    __syncthreads();                                    // all reads of reg / tables / atomics done
+    __syncthreads();                                    // all reads of reg / tables / table-gradient turns done
     if (diag) {
         // Table gradients of the wrapped-diagonal sweep, in a FIXED order (no float atomics: the same bits on every run).  Lane
         // delta of a sequence holds the sums for the entries d_hi = delta + L - 1 and d_lo = delta - 1, which no other lane of

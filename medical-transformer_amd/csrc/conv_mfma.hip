@@ -313,6 +313,10 @@ __global__ __launch_bounds__(MEDT_THREADS) void conv3x3_rows16_fwd_kernel(
 // Round 5, the LDS-patch scheme of the 3x3 kernel above: a workgroup owns 8 MFMA tiles = 128 output positions of one image (8 output
 // rows of a 16-wide map, or 2 rows of a 64-wide one) x 64 output channels; the zero-padded input patch (3 x (2 R + 5) x (W + 6)) and the
 // 64 x 147 weight slab are staged in LDS ONCE and all 37 k-steps run from them -- 296 MFMAs per wave, one global round trip.
+// The 8 tiles are R = 128 / Wo WHOLE output rows of TC = Wo / 16 tiles, so the output width must DIVIDE 128 (Wo = 16, 32, 64 or 128)
+// and Ho * Wo must be a multiple of 128: at Wo = 48, 80, 96 or 112 tile 4 (w >> 1) + t would land in a row the 2 R + 5 patch rows do
+// not hold and ho0 would step R rows per 128 positions (rows written twice or never) -- conv_stem7_ok refuses those widths and they
+// take the generic forward kernels.
 //   k = (c, kh, kw) = 4 ks + (lane >> 4);  B fragment of tile (row tr, columns 16 tc ..): Ps[c][2 tr + kh][2 (16 tc + (lane & 15)) + kw]
 // --------------------------------------------------------------------------- //
 constexpr int S7_LDW = 149;                    // weight-slab row stride (147 taps + the zero 148th, odd: conflict-free fragment reads)
@@ -321,7 +325,7 @@ bool conv_stem7_ok(int Cin, int H, int W, int Cout, int K, int stride, int pad) 
     static const bool off = [] { const char* e = getenv("MEDT_CONV_STEM7"); return e && e[0] == '0'; }();
     if (off || K != 7 || stride != 2 || pad != 3 || Cin != 3 || Cout < 32 || (H & 1) || (W & 1)) return false;
     const int Ho = H / 2, Wo = W / 2;
-    if (Wo % 16 || (Ho * Wo) % 128 || Wo > 128) return false;
+    if (Wo % 16 || 128 % Wo || (Ho * Wo) % 128) return false;       // Wo in {16, 32, 64, 128}: the 8 tiles are whole rows
     const int R = 128 / Wo;                    // output rows per workgroup
     return (size_t)(3 * (2 * R + 5) * (W + 6) + S7_OT * S7_LDW) * sizeof(float) <= 64 * 1024;
 }

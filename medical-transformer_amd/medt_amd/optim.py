@@ -203,6 +203,10 @@ class FlatAdam:
             if src:
                 torch._foreach_copy_(dst, src)
 
+    def adoption_pending(self):
+        """True while a trainable parameter has not been adopted into a flat group (its next gradient arrives through `.grad`)."""
+        return any(p.requires_grad and id(p) not in self._member for p in self.params)
+
     def signature(self):
         """What a captured step depends on: group membership and which parameters are trainable."""
         return (tuple(g.numel for g in self.groups), tuple(p.requires_grad for p in self.params))

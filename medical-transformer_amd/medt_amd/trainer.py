@@ -45,6 +45,7 @@ class TrainStep:
         self._queue = None         # deferred, grouped launches (medt_amd.defer); created on first use (needs the GPU library)
         self._ce_out = None        # [loss, counted pixels, out-of-range targets] of the last step (medt cross_entropy)
         self.collective_in_graph = False                      # set by capture: the all-reduce + Adam are graph nodes
+        self._adopted_sig = None   # eager path: the optimizer signature behind the last rolled-back adoption step
 
     # ---- eager ------------------------------------------------------------
     def _fwd_bwd(self, x, y):
@@ -183,6 +184,16 @@ class TrainStep:
 
     def __call__(self, x, y):
         if not self.use_graph:
+            if x.is_cuda and self.opt.adoption_pending() and self.opt.signature() != self._adopted_sig:
+                # The step in which FlatAdam adopts parameters takes their gradients through autograd's `.grad` and immediate
+                # weight-gradient launches -- another fp32 summation order than the recorded, slot-writing launches of every later
+                # step.  The replayed path spends that step in its rolled-back warm-up; so does the eager path, so that the two
+                # perform the same updates bit for bit (once per trainable set: parameters that never receive a gradient stay
+                # pending for good).
+                snap = self._snapshot()
+                self._eager(x, y)
+                self._restore(snap)
+                self._adopted_sig = self.opt.signature()
             return self._eager(x, y)
         sig = self._signature(x, y)
         entry = self._graphs.get(sig)

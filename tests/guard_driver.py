@@ -188,6 +188,23 @@ def family_conv(run):
     TO.test_conv_block((3, 4, 1, 1, 0, False, True, False, True, 1, 1, 1), False, dev)
 
 
+# rectangular maps (H != W, neither a power of two): the planners test H and W separately, so an index that mixes them up leaves a
+# buffer only off the square diagonal.  The many-image MFMA cases (N >= 16) take minutes each on the emulator: MEDT_GUARD_FULL=1
+def family_conv_rect(run):
+    import test_ops_gpu as TO
+    dev = torch.device("cpu")
+    for case in TO.RECT_CONV_CASES:
+        if case[9] >= 16 and not FULL:
+            continue
+        for training in (True, False):
+            run.case("conv_block %s %s" % ("-".join(str(int(v)) for v in case), "train" if training else "eval"))
+            TO.test_conv_block(case, training, dev)
+    for case in TO.RECORDED_CASES:
+        if len(case) == 10:                                  # ..., N, H, W, groups
+            run.case("recorded wgrad %s" % "-".join(str(int(v)) for v in case))
+            TO.test_recorded_weight_gradient(case, dev)
+
+
 RECORDED_ROWS = ["20-24-1-1-0-1-3-6-3", "8-8-1-1-0-1-2-3-1", "16-16-3-1-1-1-2-6-1", "72-40-1-1-0-0-2-10-1", "32-64-1-2-0-1-2-16-1",
                  "16-16-3-2-1-1-2-8-1", "32-16-3-1-1-1-3-12-3"]
 
@@ -432,7 +449,7 @@ family_train_medt128.reference = lambda lib: _train_reference(lib, _medt128, _ba
 
 
 FAMILIES = {"attention": family_attention, "attention_random": family_attention_random, "attention_repair": family_attention_repair,
-            "conv": family_conv, "recorded": family_recorded, "small_ops": family_small_ops, "blocks": family_blocks,
+            "conv": family_conv, "conv_rect": family_conv_rect, "recorded": family_recorded, "small_ops": family_small_ops, "blocks": family_blocks,
             "train": family_train, "train_medt128": family_train_medt128, "offset_pointers": family_offset_pointers}
 
 

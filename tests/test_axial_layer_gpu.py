@@ -113,6 +113,24 @@ CASES = [
     ("plain", 16, 64, False, 1, 3, 7),
     ("plain", 32, 64, False, 1, 1, 64),
     ("wopos", 16, 12, False, 1, 3, 7),
+    # attention lengths that are no power of two (the networks at 96 / 160 / 192 / 384 px: L = 48, 24, 12, 6 / 80, 40 / 96 / 192), so the
+    # thresholds of axial_geom and wopos_small_ok are met between the lengths they were tuned at; rectangular maps (other != L) throughout
+    ("dynamic", 16, 48, True, 1, 2, 5),
+    ("dynamic", 16, 48, False, 2, 1, 48),
+    ("dynamic", 32, 24, True, 2, 2, 24),
+    ("dynamic", 64, 12, False, 1, 3, 12),
+    ("dynamic", 128, 6, True, 2, 2, 6),
+    ("dynamic", 16, 96, False, 1, 1, 4),
+    ("dynamic", 32, 80, True, 1, 1, 3),
+    ("plain", 16, 40, False, 1, 2, 7),
+    ("dynamic", 16, 192, True, 1, 1, 2),        # between the 128 the sweeps stop at and the longest length the layer takes (256)
+    ("gatedsig", 16, 48, True, 1, 2, 6),
+    ("wopos", 32, 12, True, 2, 4, 12),
+    ("wopos", 64, 6, False, 1, 4, 6),
+    ("wopos", 16, 24, True, 1, 4, 24),
+    ("wopos", 32, 8, True, 1, 3, 5),
+    ("wopos", 64, 4, False, 1, 5, 7),
+    ("wopos", 16, 16, True, 1, 3, 5),           # wopos_small_ok's third length (4, 8, 16) on a rectangular map: P = 240
 ]
 
 

@@ -37,18 +37,12 @@ def test_train_cli_boundary_schedule_replayed_equals_eager(tmp_path, device, emu
     """On the GPU: 6 images of 64 px in batches of 2, replayed and --eager: identical loss lines.  Under --emulate: train.py on the
     emulated device (tests/boundary_cli_driver.py --emulated), which has no graphs: the eager run alone, 2 images of 32 px.
 
-    KNOWN TO FAIL on the MI355X in its last assertion, the equality of the loss lines; everything before it holds (the six lines
-    in order, the alpha lines 0.0100 / 0.0600 / 0.1100, finite losses).  Measured, same weights and data in both runs: eager
-    1.2092 / 1.2099 / 1.2206, replayed 1.2092 / 1.2097 / 1.2205 (another box: 1.2158 / .. / 1.2209 against 1.2157 / .. / 1.2208).
-    Either mode repeats itself exactly from run to run.  The gap is not the boundary loss's: the same two commands with
-    `--loss ce+dice`, code this feature does not touch, print 1.2070 / 1.1952 / 1.1933 eager against 1.2069 / 1.1950 / 1.1934
-    replayed, and TrainStep with BoundaryLoss IS bit-identical between eager and replayed steps when both start alike
-    (tests/test_boundary_gpu.py::test_train_step_follows_alpha_without_recapture).  What differs, as far as the code shows
-    (supposed, not isolated by an experiment): train.py --eager spends its first step adopting the parameters into FlatAdam's flat
-    buffers with the gradients arriving through autograd, while the replayed run does that in warm-up steps it rolls back before
-    capture -- the difference the step tests remove by giving the eager run a rolled-back warm-up by hand; rounding-level
-    differences of the first update then grow through training-mode BatchNorm.  Making the two modes of train.py agree means
-    changing what --eager does today, which is outside this feature."""
+    This equality used to fail on the MI355X (eager 1.2092 / 1.2099 / 1.2206 against replayed 1.2092 / 1.2097 / 1.2205; the same gap
+    with `--loss ce+dice`): train.py --eager spent its first step adopting the parameters into FlatAdam's flat buffers with the
+    gradients arriving through autograd and immediate weight-gradient launches, while the replayed run does that in warm-up steps
+    it rolls back before capture, and the rounding-level difference of the first update grew through training-mode BatchNorm.
+    TrainStep's eager path now spends the adoption step in a rolled-back warm-up too (trainer.py), as the step tests always did
+    by hand, and the two modes print the same lines."""
     eager = run_train(tmp_path, "eager", emulating, ["--eager"])
     lines = re.findall(r"^(?:boundary alpha|epoch \[).*$", eager, flags=re.M)
     assert len(lines) == 6 and [l.startswith("boundary alpha") for l in lines] == [True, False] * 3, eager

@@ -20,7 +20,7 @@ import guarded_mem as G
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "tests", "guard_driver.py")
 FULL = os.environ.get("MEDT_GUARD_FULL") == "1"
-FAMILIES = ["attention", "attention_random", "attention_repair", "conv", "recorded", "small_ops", "blocks", "train"]
+FAMILIES = ["attention", "attention_random", "attention_repair", "conv", "conv_rect", "recorded", "small_ops", "blocks", "train"]
 if FULL:
     FAMILIES.append("train_medt128")                      # MedT at 128 px, N = 4: minutes per placement
 # families whose tail placement must have run calls with a pointer that is not 16-byte aligned.  What this count shows is

@@ -23,6 +23,9 @@ CASES = [
     ("both-generic-tiles-s2", 2, 1, 32, 32, 8, (16, 1), (32, 2)),
     ("mixed-families", 8, 2, 16, 16, 64, (16, 1), (32, 2)),
     ("ragged", 3, 1, 10, 10, 8, (16, 1), (32, 1)),
+    # rectangular maps: the pair kernels decode (row, column) from the handed-in block coordinates with H and W of their own member
+    ("both-fused-small-8x12", 4, 2, 8, 12, 32, (16, 1), (32, 2)),       # 192 / 48 positions per group: both the 256-thread instantiation
+    ("both-generic-tiles-24x32", 2, 1, 24, 32, 8, (16, 1), (32, 2)),    # 1536 / 384 positions: six / one and a half 256-position blocks
 ]
 
 
