@@ -411,6 +411,33 @@ int medt_window_gather(const float* image, float* windows, const int32_t* oy, co
 int medt_window_blend(const float* win_logits, float* blended, uint8_t* mask, const int32_t* oy, const int32_t* ox, int K,
                       int H, int W, int S, int ny, int nx, float threshold, void* stream);
 
+/* Test-time augmentation at inference (not in the reference; medt_amd/tta.py): the network runs on flipped and transposed
+ * copies of its input, each prediction is mapped back and the results are averaged.  A view is a 3-bit code v: bit 2
+ * transpose, bit 1 flip rows, bit 0 flip columns, the transpose first -- in torch terms, for a (..., H, W) tensor,
+ *   forward  F_v(a): t = a.transpose(-1, -2) if v & 4 else a;  F_v(a) = t.flip([-2 if v & 2] + [-1 if v & 1])
+ *   inverse  B_v(l): m = l.flip(the same dims);                B_v(l) = m.transpose(-1, -2) if v & 4 else m
+ * (0 identity, 1 left-right mirror, 2 up-down mirror, 3 rotation by 180 degrees, 4 transpose, 5 rot90(k=-1), 6 rot90(k=1),
+ * 7 anti-transpose).  `views` is a bitmask, bit v set when code v takes part, V = popcount(views); the views are visited in
+ * ascending code.  0 < views <= 0xFF; a view with bit 2 needs H == W (MEDT_EINVAL otherwise); N*V*channels*H*W must stay
+ * below 2^31 (MEDT_EUNSUPPORTED above).
+ *
+ * expand: x (N,C,H,W) -> out (N*V,C,H,W), out[n*V + j] = F_vj(x[n]) with v_j the j-th set bit: a permutation, every element
+ * a bit copy.  out must not be x.
+ *
+ * merge: view_logits (N*V,K,H,W) -> merged (N,K,H,W) = (B_v0(l_0) + B_v1(l_1) + ... + B_vV-1(l_V-1)) / (float)V: the
+ * additions in that order by the one work-item that owns the output element, then one IEEE division (V = 1: the value passes
+ * through unchanged) -- no atomics, no reassociation, bit-identical from run to run;  mask (N,H,W) uint8 {0,255} =
+ * merged[:,1] >= threshold (test.py:131-137's rule);  votes (N,H,W) uint8 = the number of views whose own mapped-back
+ * l_j[:,1] >= threshold (0 .. V).  Any of the three outputs may be NULL, not all; mask and votes need K >= 2; merged must not
+ * be view_logits.
+ *
+ * The views without bit 2 are row copies; the views with bit 2 pass through a padded tile in LDS, so no view reads or writes
+ * global memory at stride W.  16-byte accesses when W % 4 == 0 and the pointers are aligned (floats to 16 bytes, mask and
+ * votes to 4), element accesses otherwise. */
+int medt_tta_expand(const float* x, float* out, int N, int C, int H, int W, unsigned views, void* stream);
+int medt_tta_merge(const float* view_logits, float* merged, uint8_t* mask, uint8_t* votes, int N, int K, int H, int W,
+                   unsigned views, float threshold, void* stream);
+
 /* Joint augmentation of a training batch on the device (medt_amd/augment.py; the reference's JointTransform2D.__call__,
  * utils.py:70-98, does it per item with torchvision on the host): random crop, horizontal flip, colour jitter (image only)
  * and a random affine map (image and mask), in that order.

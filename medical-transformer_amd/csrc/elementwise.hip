@@ -5,6 +5,7 @@
 //   cross-entropy loss                                       (metrics.py:17-20)
 //   Adam with coupled L2 weight decay over a flat buffer     (train.py:111-112,161)
 //   sliding-window gather / blend for images larger than the network input (not in the reference)
+//   test-time augmentation: the flipped / transposed views of a batch and the mean of their logits (not in the reference)
 //   joint augmentation of uint8 batches: crop, flip, colour jitter, affine (utils.py:70-98)
 //   exact squared Euclidean distance transform of uint8 masks, for the surface-distance scores (not in the reference)
 // All HBM-bound: one element per lane, NCHW rows coalesced, per-channel constants via scalar loads.
@@ -1038,12 +1039,18 @@ __global__ __launch_bounds__(MEDT_THREADS) void seg_counts_kernel(const float* _
     }
 }
 
+// counts = 0 as a kernel, not a memset: captured behind a forward with parallel branches (InferStep), the memset node of the
+// replayed graph did not reliably run between the forward's last kernel and the counting kernel -- test.py's score line came
+// out of counts added to whatever an intermediate of the forward had left in that pool block.  Kernel after kernel is ordered.
+__global__ __launch_bounds__(MEDT_THREADS) void seg_counts_zero_kernel(int* __restrict__ counts, int n) {
+    const int i = blockIdx.x * MEDT_THREADS + threadIdx.x;
+    if (i < n) counts[i] = 0;
+}
+
 int seg_counts(const float* logits, const int64_t* target, int* counts, int N, int K, int HW, float threshold,
                hipStream_t s) {
-    if (hipMemsetAsync(counts, 0, (size_t)N * 4 * sizeof(int), s) != hipSuccess) {
-        set_error("seg_counts: memset failed");
-        return MEDT_ELAUNCH;
-    }
+    hipLaunchKernelGGL(seg_counts_zero_kernel, dim3(cdiv(N * 4, MEDT_THREADS)), dim3(MEDT_THREADS), 0, s, counts, N * 4);
+    if (int rc = launch_status("seg_counts_zero")) return rc;
     const int parts = min(cdiv(HW, MEDT_THREADS), 64);
     hipLaunchKernelGGL(seg_counts_kernel, dim3(parts, N), dim3(MEDT_THREADS), 0, s, logits, target, counts, K, HW, threshold);
     return launch_status("seg_counts");
@@ -1186,6 +1193,186 @@ int window_blend(const float* win, float* blended, uint8_t* mask, const int32_t*
         hipLaunchKernelGGL((window_blend_kernel<false>), dim3(grid_strided(items)), dim3(MEDT_THREADS), 0, s, win, blended,
                            mask, oy, ox, k0, K, H, W, S, ny, nx, threshold, items);
     return launch_status("window_blend");
+}
+
+// --------------------------------------------------------------------------- //
+// Test-time augmentation at inference (medt_amd/tta.py; not in the reference): the eight views of the dihedral group of the
+// square, numbered by a 3-bit code v -- bit 2 transpose, bit 1 flip rows, bit 0 flip columns (transpose first) -- and a set of
+// views as a bitmask, visited in ascending code.
+//   expand: x (N,C,H,W) -> out (N V,C,H,W), out[n V + j] = F_vj(x[n]), a bit copy;   F_v(a)[y,x] = a'[fy(y), fx(x)], a' = a or a^T
+//   merge:  view logits (N V,K,H,W) -> the mean of the views mapped back, B_v(l)[y,x] = l[fy(y), fx(x)], or l[fy(x), fx(y)] with
+//           bit 2, added in ascending code by the ONE work-item that owns the output element and divided by V once.
+// Both kernels: a workgroup owns one TTA_T x TTA_T tile of one plane (expand: of the source, which it reads once for all views;
+// merge: of the output), a work-item 4 consecutive x of one tile row.  The views without bit 2 are row copies, forwards or
+// reversed, register to register.  The views with bit 2 go through an LDS tile of TTA_T + 1 floats per row, so that the global
+// read and the global write both run along rows: the tile is written along its rows (bank = row + column mod 32, the 32 lanes of
+// a half wave cover 4 rows x 8 quads: all distinct) and read along its columns (tile[q4 + e][i]: the same sum).  16-byte global
+// accesses when W % 4 == 0 and the pointers are aligned (VEC4; a quad is then inside the plane or outside it as a whole, mirrored
+// or not), element accesses with per-element bounds otherwise.  Tile edges are bounds, not a second kernel.
+// --------------------------------------------------------------------------- //
+constexpr int TTA_T = 32;
+static_assert(MEDT_THREADS == TTA_T * (TTA_T / 4), "a work-item owns 4 neighbouring elements of a tile row");
+
+// 4 elements of `row` starting at logical column c of a row of length W, the row mirrored when `flip`: e -> row[fx(c + e)]
+template <bool VEC4>
+__device__ __forceinline__ void tta_load4(const float* __restrict__ row, int c, int W, bool flip, float (&v)[4]) {
+    if (VEC4) {
+        if (c < W) {
+            const float4 q = *reinterpret_cast<const float4*>(row + (flip ? W - 4 - c : c));
+            if (flip) { v[0] = q.w; v[1] = q.z; v[2] = q.y; v[3] = q.x; } else { v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (c + e < W) v[e] = row[flip ? W - 1 - c - e : c + e];
+    }
+}
+
+template <bool VEC4>
+__device__ __forceinline__ void tta_store4(float* __restrict__ row, int c, int W, bool flip, const float (&v)[4]) {
+    if (VEC4) {
+        if (c < W)
+            *reinterpret_cast<float4*>(row + (flip ? W - 4 - c : c)) =
+                flip ? make_float4(v[3], v[2], v[1], v[0]) : make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (c + e < W) row[flip ? W - 1 - c - e : c + e] = v[e];
+    }
+}
+
+template <bool VEC4>
+__global__ __launch_bounds__(MEDT_THREADS) void tta_expand_kernel(const float* __restrict__ x, float* __restrict__ out, int C,
+                                                                  int H, int W, unsigned views, int V, int tiles_x, int tiles) {
+    MEDT_STATIC_SHARED float tile[TTA_T][TTA_T + 1];
+    const int plane = blockIdx.x / tiles, tl = blockIdx.x - plane * tiles;
+    const int ty = tl / tiles_x, tx = tl - ty * tiles_x;
+    const int n = plane / C, c = plane - n * C;
+    const int i = threadIdx.x >> 3, q4 = (threadIdx.x & 7) * 4;
+    const int r0 = ty * TTA_T, c0 = tx * TTA_T;
+    const size_t HW = (size_t)H * W;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    if (r0 + i < H) tta_load4<VEC4>(x + (size_t)plane * HW + (size_t)(r0 + i) * W, c0 + q4, W, false, a);
+    if (views & 0xF0u) {                                    // (uniform: every work-item reaches the barrier)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) tile[i][q4 + e] = a[e];
+        __syncthreads();
+    }
+    int j = 0;
+    for (int v = 0; v < 8; ++v) {
+        if (!((views >> v) & 1u)) continue;
+        float* dst = out + (((size_t)n * V + j) * C + c) * HW;
+        ++j;
+        const bool fr = (v & 2) != 0, fc = (v & 1) != 0;
+        if (!(v & 4)) {                                     // source row r -> row fy(r), mirrored or not
+            const int r = r0 + i;
+            if (r < H) tta_store4<VEC4>(dst + (size_t)(fr ? H - 1 - r : r) * W, c0 + q4, W, fc, a);
+        } else {                                            // H == W: source (r, s) -> out[fy(s)][fx(r)]; this work-item: s = c0 + i
+            const int s = c0 + i;
+            float t[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[e] = tile[q4 + e][i];
+            if (s < W) tta_store4<VEC4>(dst + (size_t)(fr ? W - 1 - s : s) * W, r0 + q4, H, fc, t);
+        }
+    }
+}
+
+int tta_expand(const float* x, float* out, int N, int C, int H, int W, unsigned views, hipStream_t s) {
+    const int V = __builtin_popcount(views), tiles_x = cdiv(W, TTA_T), tiles = tiles_x * cdiv(H, TTA_T);
+    const dim3 grid((unsigned)((size_t)tiles * N * C)), block(MEDT_THREADS);
+    if ((W % 4 == 0) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0))
+        hipLaunchKernelGGL((tta_expand_kernel<true>), grid, block, 0, s, x, out, C, H, W, views, V, tiles_x, tiles);
+    else
+        hipLaunchKernelGGL((tta_expand_kernel<false>), grid, block, 0, s, x, out, C, H, W, views, V, tiles_x, tiles);
+    return launch_status("tta_expand");
+}
+
+// merged[n,k] = (B_v0(l_0) + B_v1(l_1) + ... ) / V, the additions in that order, one IEEE division (none for V = 1: the value
+// passes through); mask = 255 (merged[n,1] >= threshold); votes = the number of views with their own l_j[n,1] >= threshold.
+// The planes are k0 .. k0 + nk - 1 of every image: all K, or the foreground channel alone when merged is not asked for.
+template <bool VEC4>
+__global__ __launch_bounds__(MEDT_THREADS) void tta_merge_kernel(const float* __restrict__ lg, float* __restrict__ merged,
+                                                                 uint8_t* __restrict__ mask, uint8_t* __restrict__ votes, int k0,
+                                                                 int nk, int K, int H, int W, unsigned views, int V,
+                                                                 float threshold, int tiles_x, int tiles) {
+    MEDT_STATIC_SHARED float tile[TTA_T][TTA_T + 1];
+    const int plane = blockIdx.x / tiles, tl = blockIdx.x - plane * tiles;
+    const int ty = tl / tiles_x, tx = tl - ty * tiles_x;
+    const int n = plane / nk, k = k0 + (plane - n * nk);
+    const int i = threadIdx.x >> 3, q4 = (threadIdx.x & 7) * 4;
+    const int y0 = ty * TTA_T, x0 = tx * TTA_T, y = y0 + i;
+    const size_t HW = (size_t)H * W;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    int agree[4] = {0, 0, 0, 0};
+    int j = 0;
+    for (int v = 0; v < 8; ++v) {
+        if (!((views >> v) & 1u)) continue;
+        const float* src = lg + (((size_t)n * V + j) * K + k) * HW;
+        const bool fr = (v & 2) != 0, fc = (v & 1) != 0;
+        float l[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!(v & 4)) {
+            if (y < H) tta_load4<VEC4>(src + (size_t)(fr ? H - 1 - y : y) * W, x0 + q4, W, fc, l);
+        } else {
+            // H == W.  B[y][x] = l[fy(x)][fx(y)]: stage tile[a][b] = l[fy(x0 + a)][fx(y0 + b)] by row reads (un-mirrored on the
+            // way in), then this work-item's B[y0 + i][x0 + q4 + e] = tile[q4 + e][i]
+            float t[4] = {0.f, 0.f, 0.f, 0.f};
+            const int sx = x0 + i;
+            if (sx < W) tta_load4<VEC4>(src + (size_t)(fr ? H - 1 - sx : sx) * W, y0 + q4, H, fc, t);
+            __syncthreads();                                // the previous transposing view's readers are done
+#pragma unroll
+            for (int e = 0; e < 4; ++e) tile[i][q4 + e] = t[e];
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < 4; ++e) l[e] = tile[q4 + e][i];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[e] = j == 0 ? l[e] : acc[e] + l[e];
+            agree[e] += l[e] >= threshold ? 1 : 0;
+        }
+        ++j;
+    }
+    if (y >= H || x0 + q4 >= W) return;
+    if (V > 1) {
+        const float fv = (float)V;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = acc[e] / fv;
+    }
+    const size_t px = (size_t)y * W + x0 + q4;
+    if (merged) tta_store4<VEC4>(merged + ((size_t)n * K + k) * HW + (size_t)y * W, x0 + q4, W, false, acc);
+    if (k != 1) return;
+    if (VEC4) {
+        uint32_t m = 0, a = 0;                              // 4 bytes as one 32-bit store (little endian)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            m |= (acc[e] >= threshold ? 255u : 0u) << (8 * e);
+            a |= (uint32_t)agree[e] << (8 * e);
+        }
+        if (mask) *reinterpret_cast<uint32_t*>(mask + (size_t)n * HW + px) = m;
+        if (votes) *reinterpret_cast<uint32_t*>(votes + (size_t)n * HW + px) = a;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (x0 + q4 + e >= W) break;
+            if (mask) mask[(size_t)n * HW + px + e] = acc[e] >= threshold ? 255 : 0;
+            if (votes) votes[(size_t)n * HW + px + e] = (uint8_t)agree[e];
+        }
+    }
+}
+
+int tta_merge(const float* view_logits, float* merged, uint8_t* mask, uint8_t* votes, int N, int K, int H, int W, unsigned views,
+              float threshold, hipStream_t s) {
+    const int V = __builtin_popcount(views), tiles_x = cdiv(W, TTA_T), tiles = tiles_x * cdiv(H, TTA_T);
+    const int k0 = merged ? 0 : 1, nk = merged ? K : 1;         // mask / votes only: the foreground channel alone
+    const dim3 grid((unsigned)((size_t)tiles * N * nk)), block(MEDT_THREADS);
+    if ((W % 4 == 0) && ((uintptr_t)view_logits % 16 == 0) && ((uintptr_t)merged % 16 == 0) && ((uintptr_t)mask % 4 == 0) &&
+        ((uintptr_t)votes % 4 == 0))
+        hipLaunchKernelGGL((tta_merge_kernel<true>), grid, block, 0, s, view_logits, merged, mask, votes, k0, nk, K, H, W, views,
+                           V, threshold, tiles_x, tiles);
+    else
+        hipLaunchKernelGGL((tta_merge_kernel<false>), grid, block, 0, s, view_logits, merged, mask, votes, k0, nk, K, H, W, views,
+                           V, threshold, tiles_x, tiles);
+    return launch_status("tta_merge");
 }
 
 // --------------------------------------------------------------------------- //

@@ -1057,6 +1057,30 @@ int medt_window_blend(const float* win_logits, float* blended, uint8_t* mask, co
     return window_blend(win_logits, blended, mask, oy, ox, K, H, W, S, ny, nx, threshold, (hipStream_t)stream);
 }
 
+static int tta_args(const char* what, bool pointers_ok, int N, int CK, int H, int W, unsigned views) {
+    if (!pointers_ok || N < 1 || CK < 1 || H < 1 || W < 1 || views == 0 || views > 0xFFu) {
+        set_error("%s: bad arguments (N %d, %d planes of %d x %d, views 0x%x)", what, N, CK, H, W, views); return MEDT_EINVAL;
+    }
+    if ((views & 0xF0u) && H != W) {
+        set_error("%s: views 0x%x transpose, which needs a square map (%d x %d)", what, views, H, W); return MEDT_EINVAL;
+    }
+    if ((double)N * __builtin_popcount(views) * CK * H * W >= 2147483648.0) {
+        set_error("%s: %d x %d views of %d x %d x %d: 2^31 elements or more", what, N, __builtin_popcount(views), CK, H, W);
+        return MEDT_EUNSUPPORTED;
+    }
+    return MEDT_OK;
+}
+int medt_tta_expand(const float* x, float* out, int N, int C, int H, int W, unsigned views, void* stream) {
+    if (int rc = tta_args("tta_expand", x && out && x != out, N, C, H, W, views)) return rc;
+    return tta_expand(x, out, N, C, H, W, views, (hipStream_t)stream);
+}
+int medt_tta_merge(const float* view_logits, float* merged, uint8_t* mask, uint8_t* votes, int N, int K, int H, int W,
+                   unsigned views, float threshold, void* stream) {
+    const bool ok = view_logits && (merged || mask || votes) && merged != view_logits && !((mask || votes) && K < 2);
+    if (int rc = tta_args("tta_merge", ok, N, K, H, W, views)) return rc;
+    return tta_merge(view_logits, merged, mask, votes, N, K, H, W, views, threshold, (hipStream_t)stream);
+}
+
 size_t medt_augment_param_floats(void) { return augment_param_floats(); }
 
 static bool augment_geometry_ok(const char* what, int N, int H, int W, int C, int th, int tw) {

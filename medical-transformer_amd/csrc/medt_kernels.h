@@ -122,6 +122,10 @@ int window_gather(const float* image, float* windows, const int32_t* oy, const i
                   int ny, int nx, hipStream_t s);
 int window_blend(const float* win, float* blended, uint8_t* mask, const int32_t* oy, const int32_t* ox, int K, int H, int W,
                  int S, int ny, int nx, float threshold, hipStream_t s);
+// test-time augmentation: the flipped / transposed views of a batch, and the mean of the view logits mapped back (medt_abi.h)
+int tta_expand(const float* x, float* out, int N, int C, int H, int W, unsigned views, hipStream_t s);
+int tta_merge(const float* view_logits, float* merged, uint8_t* mask, uint8_t* votes, int N, int K, int H, int W, unsigned views,
+              float threshold, hipStream_t s);
 size_t augment_param_floats();
 int augment_parts(int th, int tw);                 // partial sums per image of augment_stats
 // workspace: N*augment_parts() partial sums, then N means (what the contrast slot of each record used)

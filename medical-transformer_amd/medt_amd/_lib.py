@@ -154,6 +154,8 @@ SIGNATURES = {
     "medt_seg_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "medt_window_gather": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
     "medt_window_blend": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_float, C.c_void_p]),
+    "medt_tta_expand": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_uint, C.c_void_p]),
+    "medt_tta_merge": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_uint, C.c_float, C.c_void_p]),
     "medt_augment_param_floats": (C.c_size_t, []),
     "medt_augment_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "medt_augment_stats": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p]),

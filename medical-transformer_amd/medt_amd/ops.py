@@ -849,6 +849,61 @@ def window_blend(win_logits, oy, ox, H, W, threshold=0.5, want_logits=True, want
 
 
 # --------------------------------------------------------------------------- #
+# test-time augmentation: flipped / transposed views and the mean of their logits (medt_amd.tta)
+# --------------------------------------------------------------------------- #
+def _tta_views(what, views, H, W):
+    views = int(views)
+    if not 0 < views <= 0xFF:
+        raise L.MedtError(f"{what}: views is a bitmask 0x01 .. 0xFF over the eight view codes (got {views:#x})")
+    if views & 0xF0 and H != W:
+        raise L.MedtError(f"{what}: views {views:#x} transpose, which needs square maps (got {H} x {W})")
+    return views, bin(views).count("1")
+
+
+def tta_expand(x, views, out=None):
+    """(N,C,H,W) -> (N*V,C,H,W): out[n*V + j] = the j-th view (ascending code; bit 2 transpose, bit 1 flip rows, bit 0 flip
+    columns) of x[n], a bit copy.  `out`: a contiguous float32 buffer whose first N*V items are written (TtaInfer keeps the
+    padding of its last batch behind them)."""
+    _require_device(x)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise L.MedtError("tta_expand: a float32 (N,C,H,W) batch expected")
+    x = x.contiguous()
+    N, Cc, H, W = x.shape
+    views, V = _tta_views("tta_expand", views, H, W)
+    if out is None:
+        out = torch.empty((N * V, Cc, H, W), device=x.device, dtype=torch.float32)
+    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device or out.dim() != 4
+          or out.shape[0] < N * V or tuple(out.shape[1:]) != (Cc, H, W)):
+        raise L.MedtError("tta_expand: out must be a contiguous float32 (>=N*V,C,H,W) tensor on the input's device")
+    L.check(L.lib().medt_tta_expand(x.data_ptr(), out.data_ptr(), N, Cc, H, W, views, _stream()), "medt_tta_expand")
+    return out[:N * V]
+
+
+def tta_merge(view_logits, views, threshold=0.5, want_logits=True, want_mask=True, want_votes=False):
+    """(N*V,K,H,W) view logits -> (merged (N,K,H,W) float32 or None, mask (N,H,W) uint8 {0,255} or None[, votes (N,H,W) uint8]):
+    merged = the views mapped back, added in ascending code and divided by V; mask = merged[:,1] >= threshold; votes = how
+    many views' own mapped-back foreground logit reaches the threshold (returned as a third item when asked for)."""
+    _require_device(view_logits)
+    if view_logits.dim() != 4 or view_logits.dtype != torch.float32:
+        raise L.MedtError("tta_merge: float32 (N*V,K,H,W) view logits expected")
+    if not (want_logits or want_mask or want_votes):
+        raise L.MedtError("tta_merge: nothing asked for")
+    view_logits = view_logits.contiguous()
+    NV, K, H, W = view_logits.shape
+    views, V = _tta_views("tta_merge", views, H, W)
+    if NV < V or NV % V:
+        raise L.MedtError(f"tta_merge: {NV} view logits for sets of {V} views")
+    N = NV // V
+    dev = view_logits.device
+    merged = torch.empty((N, K, H, W), device=dev, dtype=torch.float32) if want_logits else None
+    mask = torch.empty((N, H, W), device=dev, dtype=torch.uint8) if want_mask else None
+    votes = torch.empty((N, H, W), device=dev, dtype=torch.uint8) if want_votes else None
+    L.check(L.lib().medt_tta_merge(view_logits.data_ptr(), L.ptr(merged), L.ptr(mask), L.ptr(votes), N, K, H, W, views,
+                                   float(threshold), _stream()), "medt_tta_merge")
+    return (merged, mask, votes) if want_votes else (merged, mask)
+
+
+# --------------------------------------------------------------------------- #
 # joint augmentation of uint8 batches (medt_amd.augment)
 # --------------------------------------------------------------------------- #
 AUG_CONTRAST = 2.0          # operation code of a contrast slot (include/medt_abi.h)

@@ -52,15 +52,23 @@ class WindowInfer:
 
     The T windows run `gather` per forward replay; the last, shorter batch is padded with copies of its last window and
     the padding's logits are dropped (test.py's rule for its last batch).  In eval mode the windows of a batch do not
-    interact; in train mode they would (batch statistics), so a model in train mode is refused."""
+    interact; in train mode they would (batch statistics), so a model in train mode is refused.
 
-    def __init__(self, model, size: int, gather: int = 4, stride: int = None, threshold: float = 0.5, use_graph: bool = True):
+    tta = "flips" | "d4" | a view bitmask (medt_amd.tta): every window is averaged over the views before the blend,
+    window_blend(tta_merge(infer(tta_expand(windows)))); tta=None (the default) is the path above, launch for launch."""
+
+    def __init__(self, model, size: int, gather: int = 4, stride: int = None, threshold: float = 0.5, use_graph: bool = True,
+                 tta=None):
         self.model, self.size, self.gather, self.threshold = model, int(size), max(1, int(gather)), float(threshold)
         self.stride = max(1, self.size // 2) if stride is None else int(stride)
         if not 1 <= self.stride <= self.size:
             raise L.MedtError(f"WindowInfer: 1 <= stride <= size expected (stride {self.stride}, size {self.size})")
         self.infer = InferStep(model, use_graph=use_graph, threshold=threshold)
         self._plans = {}
+        self.views = None
+        if tta is not None:
+            from .tta import parse_views
+            self.views = parse_views(tta)
 
     def _plan(self, H, W, device):
         key = (H, W, str(device))
@@ -87,6 +95,12 @@ class WindowInfer:
         S, g = self.size, self.gather
         oy, ox = self._plan(H, W, image.device)
         T = oy.numel() * ox.numel()
+        if self.views is not None:
+            logits = self._tta_windows(image, oy, ox, T)
+            blended, mask = ops.window_blend(logits, oy, ox, H, W, self.threshold)
+            if target is None:
+                return blended, mask
+            return blended, mask, ops.seg_counts(blended.unsqueeze(0), target.reshape(1, H, W), self.threshold)
         Tpad = -(-T // g) * g
         windows = torch.empty((Tpad, Cc, S, S), device=image.device, dtype=torch.float32)
         ops.window_gather(image, oy, ox, S, out=windows)
@@ -104,3 +118,17 @@ class WindowInfer:
             return blended, mask
         counts = ops.seg_counts(blended.unsqueeze(0), target.reshape(1, H, W), self.threshold)
         return blended, mask, counts
+
+    def _tta_windows(self, image, oy, ox, T):
+        """The T windows' logits averaged over the views (medt_amd.tta): the T V views run `gather` per replay, padded like
+        the windows, and are merged per window -- what the blend receives is one (T,K,S,S) stack, as without views."""
+        from .tta import run_padded
+        S, g = self.size, self.gather
+        windows = ops.window_gather(image, oy, ox, S)
+        n = T * bin(self.views).count("1")
+        npad = -(-n // g) * g
+        batch = torch.empty((npad, image.shape[0], S, S), device=image.device, dtype=torch.float32)
+        ops.tta_expand(windows, self.views, out=batch)
+        if npad > n:
+            batch[n:] = batch[n - 1]
+        return ops.tta_merge(run_padded(self.infer, batch, n, g), self.views, self.threshold, want_mask=False)[0]

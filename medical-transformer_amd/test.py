@@ -5,7 +5,8 @@ thresholded channel-1 prediction of every validation image as <direc>/<filename>
 undefined args.aug (test.py:62) and dies; here the flag exists and is ignored.  --surface on adds the surface-distance scores
 (HD, HD95, ASSD) of the written masks behind the F1 / mIoU / PA line, --objects on the object-level scores (object F1 and Dice,
 AJI, PQ) behind those, --object_hausdorff on the object-level Hausdorff distance of GlaS behind those; --fill_holes on and
---min_object AREA clean the masks on the device before they are written and scored."""
+--min_object AREA clean the masks on the device before they are written and scored; --tta flips|d4 averages the logits of the
+mirrored (and rotated) views of every image or window before the mask is taken (medt_amd.tta)."""
 import argparse
 import os
 
@@ -47,6 +48,11 @@ parser.add_argument('--window', default='off', choices=['off', 'on'],
                          'device, the windows run --gather per replay and their logits are blended into a map of the '
                          "image's own size (medt_amd.window.WindowInfer)")
 parser.add_argument('--window_stride', type=int, default=None, help='window step in pixels with --window on (default: imgsize / 2)')
+parser.add_argument('--tta', default='off', choices=['off', 'flips', 'd4'],
+                    help='(not in the reference) test-time augmentation: the network also runs on mirrored (flips: 4 views) or '
+                         'mirrored and rotated (d4: 8 views, square inputs) copies of every image or window, the logits are '
+                         'mapped back and averaged on the device, and every mask, PNG and score line describes the average '
+                         '(medt_amd.tta.TtaInfer)')
 parser.add_argument('--surface', default='off', choices=['off', 'on'],
                     help='(not in the reference) on: a second score line with the surface-distance scores of the written masks '
                          'against the label maps -- Hausdorff distance, its 95th percentile and the average symmetric surface '
@@ -135,7 +141,10 @@ def main():
     def run(items):
         xs = torch.cat([it[0] for it in items] + [items[-1][0]] * (gather - len(items))).to(device)
         ys = torch.cat([it[1].long().reshape(1, *it[0].shape[2:]) for it in items] + [items[-1][1].long().reshape(1, *items[-1][0].shape[2:])] * (gather - len(items))).to(device)
-        y_out, counts = infer(xs, ys)
+        if tta_infer is not None:      # the views of the batch, `gather` per replay; logits and counts of their mean
+            y_out, _, counts = tta_infer(xs[:len(items)], ys[:len(items)])
+        else:
+            y_out, counts = infer(xs, ys)
         if cleaning:
             mask, cleaned = clean((y_out[:len(items), 1] >= 0.5).to(torch.uint8) * 255, ys[:len(items)], counts)
             scores.append(cleaned)
@@ -153,11 +162,16 @@ def main():
 
     gather = max(1, args.gather)
     pending = []
+    tta_infer = None
+    if args.tta != "off" and args.window != "on":
+        from medt_amd.tta import TtaInfer
+        tta_infer = TtaInfer(model, args.tta, gather=gather)
     if args.window == "on":
         # every loader item may have its own H x W: one image at a time, its windows `gather` per replay; the PNG has the
         # image's size and the counts are those of the whole image
         from medt_amd.window import WindowInfer
-        winfer = WindowInfer(model, args.imgsize, gather=gather, stride=args.window_stride)
+        winfer = WindowInfer(model, args.imgsize, gather=gather, stride=args.window_stride,
+                             tta=None if args.tta == "off" else args.tta)
         for batch_idx, (X_batch, y_batch, *rest) in enumerate(valloader):
             image_filename = rest[0][0] if isinstance(rest[0][0], str) else '%s.png' % str(batch_idx + 1).zfill(3)
             target = y_batch.long().reshape(1, *X_batch.shape[2:]).to(device)
