@@ -48,6 +48,12 @@ def imwrite(path, arr):
     Image.fromarray(arr.astype(np.uint8)).save(path)
 
 
+def item_filename(rest, batch_idx):
+    """The file name test.py and train.py's validation write a loader item under: the dataset's own (the third entry of the
+    item, batched) or, from a dataset that gives none, the item's 1-based position (reference test.py:111-114, train.py:176-179)."""
+    return rest[0][0] if isinstance(rest[0][0], str) else '%s.png' % str(batch_idx + 1).zfill(3)
+
+
 def to_tensor(img_hwc_uint8):
     return torch.from_numpy(np.ascontiguousarray(img_hwc_uint8.transpose(2, 0, 1))).float().div_(255.0)
 

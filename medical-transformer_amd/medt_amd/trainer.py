@@ -305,3 +305,29 @@ class InferStep:
             static_t.copy_(target)
         graph.replay()
         return out if target is None else (out, counts)
+
+
+def padded_batch(n, gather, shape, device, dtype=torch.float32):
+    """An uninitialised (ceil(n / gather) gather, *shape) batch for run_padded: the caller fills its first n rows."""
+    return torch.empty((-(-n // gather) * gather,) + tuple(shape), device=device, dtype=dtype)
+
+
+def run_padded(infer, batch, n, gather, target=None):
+    """The first n rows of `batch` (see padded_batch) through `infer`, `gather` per call -> (n, ...) logits, or (logits, (n,4)
+    counts) when label maps `target`, padded like the batch, are given: fresh tensors.  The rows behind n are filled here with
+    copies of row n - 1 (same graph for the last, shorter batch; their outputs are dropped).  A replay's outputs are static --
+    the next replay overwrites them -- so every call's are copied away."""
+    if batch.shape[0] > n:
+        batch[n:] = batch[n - 1]
+        if target is not None:
+            target[n:] = target[n - 1]
+    outs = None
+    for b in range(0, n, gather):
+        got = infer(batch[b:b + gather]) if target is None else infer(batch[b:b + gather], target[b:b + gather])
+        got = (got,) if target is None else got
+        if outs is None:
+            outs = tuple(torch.empty((n,) + tuple(o.shape[1:]), device=o.device, dtype=o.dtype) for o in got)
+        m = min(gather, n - b)
+        for dst, o in zip(outs, got):
+            dst[b:b + m].copy_(o[:m])
+    return outs[0] if target is None else outs

@@ -12,11 +12,9 @@ view's logits back, adds them in ascending code and divides by V once -- one wor
 same bits on every run.  Logits are averaged, not probabilities: the project thresholds and blends logits everywhere."""
 from __future__ import annotations
 
-import torch
-
 from . import _lib as L
 from . import ops
-from .trainer import InferStep
+from .trainer import InferStep, padded_batch, run_padded
 
 VIEWS_OFF = 0x01
 VIEWS_FLIPS = 0x0F
@@ -39,20 +37,6 @@ def view_codes(views) -> list:
     """The codes of a set of views, ascending: the order of tta_expand's outputs and of tta_merge's sum."""
     views = parse_views(views)
     return [v for v in range(8) if views >> v & 1]
-
-
-def run_padded(infer, batch, n, gather):
-    """`batch` (>= ceil(n / gather) gather, ...): its first n items through `infer`, `gather` per call -> (n, ...) logits, a fresh
-    tensor.  The caller has filled the items behind n with copies of item n - 1 (test.py's rule for its last batch); their
-    logits are dropped.  The replay's outputs are static -- the next replay overwrites them -- so they are copied away."""
-    logits = None
-    for b in range(0, n, gather):
-        out = infer(batch[b:b + gather])
-        if logits is None:
-            logits = torch.empty((n,) + tuple(out.shape[1:]), device=batch.device, dtype=torch.float32)
-        m = min(gather, n - b)
-        logits[b:b + m].copy_(out[:m])
-    return logits
 
 
 class TtaInfer:
@@ -82,14 +66,9 @@ class TtaInfer:
             raise L.MedtError("TtaInfer: a (N,C,H,W) batch expected")
         x = x.contiguous()
         N, Cc, H, W = x.shape
-        g, n = self.gather, N * self.V
-        npad = -(-n // g) * g
-        batch = torch.empty((npad, Cc, H, W), device=x.device, dtype=torch.float32)
+        batch = padded_batch(N * self.V, self.gather, (Cc, H, W), x.device)
         ops.tta_expand(x, self.views, out=batch)
-        if npad > n:
-            batch[n:] = batch[n - 1]
-        logits = run_padded(self.infer, batch, n, g)
-        merged, mask = ops.tta_merge(logits, self.views, self.threshold)
+        merged, mask = ops.tta_merge(run_padded(self.infer, batch, N * self.V, self.gather), self.views, self.threshold)
         if target is None:
             return merged, mask
         return merged, mask, ops.seg_counts(merged, target.reshape(N, H, W), self.threshold)

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .trainer import InferStep
+from .trainer import InferStep, padded_batch, run_padded
 
 
 def _axis_origins(D: int, S: int, stride: int):
@@ -55,7 +55,7 @@ class WindowInfer:
     interact; in train mode they would (batch statistics), so a model in train mode is refused.
 
     tta = "flips" | "d4" | a view bitmask (medt_amd.tta): every window is averaged over the views before the blend,
-    window_blend(tta_merge(infer(tta_expand(windows)))); tta=None (the default) is the path above, launch for launch."""
+    blend(tta_merge(infer(tta_expand(windows)))); tta=None (the default) is the path above, launch for launch."""
 
     def __init__(self, model, size: int, gather: int = 4, stride: int = None, threshold: float = 0.5, use_graph: bool = True,
                  tta=None):
@@ -94,41 +94,16 @@ class WindowInfer:
         Cc, H, W = image.shape
         S, g = self.size, self.gather
         oy, ox = self._plan(H, W, image.device)
-        T = oy.numel() * ox.numel()
+        n = oy.numel() * ox.numel() * (1 if self.views is None else bin(self.views).count("1"))
+        batch = padded_batch(n, g, (Cc, S, S), image.device)
+        if self.views is None:
+            ops.window_gather(image, oy, ox, S, out=batch)
+        else:                     # the views of every window: what the blend receives is one stack per window either way
+            ops.tta_expand(ops.window_gather(image, oy, ox, S), self.views, out=batch)
+        logits = run_padded(self.infer, batch, n, g)
         if self.views is not None:
-            logits = self._tta_windows(image, oy, ox, T)
-            blended, mask = ops.window_blend(logits, oy, ox, H, W, self.threshold)
-            if target is None:
-                return blended, mask
-            return blended, mask, ops.seg_counts(blended.unsqueeze(0), target.reshape(1, H, W), self.threshold)
-        Tpad = -(-T // g) * g
-        windows = torch.empty((Tpad, Cc, S, S), device=image.device, dtype=torch.float32)
-        ops.window_gather(image, oy, ox, S, out=windows)
-        if Tpad > T:
-            windows[T:] = windows[T - 1]
-        logits = None
-        for b in range(0, T, g):
-            out = self.infer(windows[b:b + g])
-            if logits is None:
-                logits = torch.empty((T,) + tuple(out.shape[1:]), device=image.device, dtype=torch.float32)
-            n = min(g, T - b)
-            logits[b:b + n].copy_(out[:n])         # the replay's outputs are static: the next replay overwrites them
+            logits = ops.tta_merge(logits, self.views, self.threshold, want_mask=False)[0]
         blended, mask = ops.window_blend(logits, oy, ox, H, W, self.threshold)
         if target is None:
             return blended, mask
-        counts = ops.seg_counts(blended.unsqueeze(0), target.reshape(1, H, W), self.threshold)
-        return blended, mask, counts
-
-    def _tta_windows(self, image, oy, ox, T):
-        """The T windows' logits averaged over the views (medt_amd.tta): the T V views run `gather` per replay, padded like
-        the windows, and are merged per window -- what the blend receives is one (T,K,S,S) stack, as without views."""
-        from .tta import run_padded
-        S, g = self.size, self.gather
-        windows = ops.window_gather(image, oy, ox, S)
-        n = T * bin(self.views).count("1")
-        npad = -(-n // g) * g
-        batch = torch.empty((npad, image.shape[0], S, S), device=image.device, dtype=torch.float32)
-        ops.tta_expand(windows, self.views, out=batch)
-        if npad > n:
-            batch[n:] = batch[n - 1]
-        return ops.tta_merge(run_padded(self.infer, batch, n, g), self.views, self.threshold, want_mask=False)[0]
+        return blended, mask, ops.seg_counts(blended.unsqueeze(0), target.reshape(1, H, W), self.threshold)

@@ -236,6 +236,25 @@ def _object_scores_image(ap, ag, rows):
     return f1, dice, aji, dq * sq, dq, sq
 
 
+def _object_tables(pred, target, connectivity, labelled):
+    """What object_scores and object_hausdorff both start from -> (label maps (lp, lg), object counts on the device (cp, cg),
+    the counts as lists, the area tables on the host, the overlap rows (n, j, i, |G_i ∩ P_j|) as a list).  Masks are labelled here
+    at `connectivity`; with labelled=True the label maps are taken as given and the counts are their maxima."""
+    from medt_amd import ops
+    if labelled:
+        lp, lg = pred, target
+        N = lp.reshape(-1, *lp.shape[-2:]).shape[0]
+        cp = lp.reshape(N, -1).amax(dim=1).to(torch.int32)
+        cg = lg.reshape(N, -1).amax(dim=1).to(torch.int32)
+    else:
+        lp, cp = ops.label(pred, connectivity)
+        lg, cg = ops.label(target, connectivity)
+    area_p, _ = ops.label_tables(lp, cp)
+    area_g, _ = ops.label_tables(lg, cg)
+    rows = ops.label_overlaps(lp, cp, lg, cg).cpu().tolist()
+    return (lp, lg), (cp, cg), (cp.cpu().tolist(), cg.cpu().tolist()), (area_p.cpu(), area_g.cpu()), rows
+
+
 def object_scores(pred, target, connectivity=8, labelled=False):
     """Per-image object-level scores of a prediction against a target, on the device.  pred / target: uint8 masks (N,H,W) or
     (H,W), foreground = mask != 0, labelled here at `connectivity` (4 or 8; 8 is MATLAB's bwlabel); or with labelled=True int32
@@ -258,19 +277,8 @@ def object_scores(pred, target, connectivity=8, labelled=False):
 
     Labelling, the area tables and the overlap table run on the device (medt_amd.ops.label / label_tables / label_overlaps);
     only those integer tables come to the host, where the scores are computed in float64 per image."""
-    from medt_amd import ops
-    if labelled:
-        lp, lg = pred, target
-        N = lp.reshape(-1, *lp.shape[-2:]).shape[0]
-        cp = lp.reshape(N, -1).amax(dim=1).to(torch.int32)
-        cg = lg.reshape(N, -1).amax(dim=1).to(torch.int32)
-    else:
-        lp, cp = ops.label(pred, connectivity)
-        lg, cg = ops.label(target, connectivity)
-    area_p, _ = ops.label_tables(lp, cp)
-    area_g, _ = ops.label_tables(lg, cg)
-    rows = ops.label_overlaps(lp, cp, lg, cg).cpu().tolist()
-    area_p, area_g, cp, cg = area_p.cpu().tolist(), area_g.cpu().tolist(), cp.cpu().tolist(), cg.cpu().tolist()
+    _, _, (cp, cg), (area_p, area_g), rows = _object_tables(pred, target, connectivity, labelled)
+    area_p, area_g = area_p.tolist(), area_g.tolist()
     N = len(cp)
     per_image = [[] for _ in range(N)]
     for n, j, i, I in rows:
@@ -334,22 +342,10 @@ def object_hausdorff(pred, target, connectivity=8, labelled=False, prune=True):
     import math
     import numpy as np
     from medt_amd import ops
-    if labelled:
-        lp, lg = pred, target
-        N = lp.reshape(-1, *lp.shape[-2:]).shape[0]
-        cp = lp.reshape(N, -1).amax(dim=1).to(torch.int32)
-        cg = lg.reshape(N, -1).amax(dim=1).to(torch.int32)
-    else:
-        lp, cp = ops.label(pred, connectivity)
-        lg, cg = ops.label(target, connectivity)
-    area_p, _ = ops.label_tables(lp, cp)
-    area_g, _ = ops.label_tables(lg, cg)
-    box_p, box_g = ops.label_boxes(lp, cp).cpu(), ops.label_boxes(lg, cg).cpu()
-    rows = ops.label_overlaps(lp, cp, lg, cg).cpu().tolist()
-    area_p, area_g = area_p.cpu().numpy().astype(np.int64), area_g.cpu().numpy().astype(np.int64)
+    (lp, lg), (cp_dev, cg_dev), (cp, cg), (area_p, area_g), rows = _object_tables(pred, target, connectivity, labelled)
+    box_p, box_g = ops.label_boxes(lp, cp_dev).cpu(), ops.label_boxes(lg, cg_dev).cpu()
+    area_p, area_g = area_p.numpy().astype(np.int64), area_g.numpy().astype(np.int64)
     bp, bg = box_p.numpy().astype(np.int64), box_g.numpy().astype(np.int64)
-    cp_dev, cg_dev = cp, cg
-    cp, cg = cp.cpu().tolist(), cg.cpu().tolist()
     N = len(cp)
     out = {"hd": torch.full((N,), float("nan"), dtype=torch.float64), "pairs": torch.zeros(N, dtype=torch.int64),
            "n_pred": torch.tensor(cp, dtype=torch.int64), "n_gt": torch.tensor(cg, dtype=torch.int64)}

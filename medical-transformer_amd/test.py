@@ -10,15 +10,14 @@ mirrored (and rotated) views of every image or window before the mask is taken (
 import argparse
 import os
 
-import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
 import lib
 import medt_amd
 import metrics
-from medt_amd.data import imwrite
-from medt_amd.trainer import InferStep
+from medt_amd.data import imwrite, item_filename
+from medt_amd.trainer import InferStep, padded_batch, run_padded
 
 parser = argparse.ArgumentParser(description='MedT')
 parser.add_argument('-j', '--workers', default=16, type=int, metavar='N', help='number of data loading workers (default: 8)')
@@ -78,6 +77,41 @@ parser.add_argument('--fill_holes', default='off', choices=['off', 'on'],
                     help='(not in the reference) on: the holes of every mask are filled before small objects are removed and the '
                          'mask is written and scored (medt_amd.ops.fill_holes = scipy.ndimage.binary_fill_holes)')
 
+# the score lines behind "images ...": (line prefix = the flag's name with a blank for its underscore, metric of a {0,255} mask
+# batch and a {0,1} target batch on the device -> per-batch dictionary with "valid", the keys the line shows, their labels)
+SUMMARY = (("surface", lambda mask, t, conn: metrics.surface_scores(mask, t), ("hd", "hd95", "assd"), ("HD", "HD95", "ASSD")),
+           ("objects", metrics.object_scores, ("f1", "dice", "aji", "pq"), ("F1obj", "Diceobj", "AJI", "PQ")),
+           ("object hausdorff", metrics.object_hausdorff, ("hd",), ("Hobj",)))
+
+
+def group_items(loader, gather):
+    """The loader's items as (X, y, file name), in runs of at most `gather` consecutive items of equal image shape: what one
+    forward replay takes.  gather = 1 gives single items."""
+    pending = []
+    for batch_idx, (X_batch, y_batch, *rest) in enumerate(loader):
+        if pending and pending[0][0].shape != X_batch.shape:
+            yield pending
+            pending = []
+        pending.append((X_batch, y_batch, item_filename(rest, batch_idx)))
+        if len(pending) == gather:
+            yield pending
+            pending = []
+    if pending:
+        yield pending
+
+
+def images_line(counts):
+    f1, iou, pa = metrics.segmentation_scores(counts)
+    return "images {}  F1 {:.4f}  mIoU {:.4f}  PA {:.4f}".format(len(f1), f1.mean().item(), iou.mean().item(), pa.mean().item())
+
+
+def summary_line(prefix, keys, labels, batches):
+    """One line of SUMMARY from its per-batch dictionaries: the means over the valid images, nan when there is none."""
+    valid = torch.cat([s["valid"] for s in batches])
+    means = [v.mean().item() if len(v) else float("nan") for v in (torch.cat([s[k] for s in batches])[valid] for k in keys)]
+    return "{} images {}/{}".format(prefix, int(valid.sum()), len(valid)) + "".join(
+        "  {} {:.4f}".format(label, m) for label, m in zip(labels, means))
+
 
 def main():
     args = parser.parse_args()
@@ -103,12 +137,10 @@ def main():
     model.eval()
     fulldir = args.direc + "/"
     os.makedirs(fulldir, exist_ok=True)
+    gather = max(1, args.gather)
     scores = []
-    surface = [] if args.surface == "on" else None     # per-batch metrics.surface_scores of (mask, target > 0), eager, behind the replay
-    objects = [] if args.objects == "on" else None     # per-batch metrics.object_scores of the same pairs
-    obj_hd = [] if args.object_hausdorff == "on" else None   # per-batch metrics.object_hausdorff of the same pairs
-    scoring = surface is not None or objects is not None or obj_hd is not None
-    cleaning = args.fill_holes == "on" or args.min_object > 0
+    # the score lines asked for, each with its per-batch dictionaries of (mask, target > 0): eager, behind the replay
+    scored = [(row, []) for row in SUMMARY if getattr(args, row[0].replace(" ", "_")) == "on"]
 
     def clean(mask, target, like):
         """The clean-ups of a uint8 {0,255} mask batch on the device, holes first, and the {tp, fp, fn, tn} counts of the result
@@ -122,98 +154,66 @@ def main():
         counts = torch.stack([(p & t).sum(1), (p & ~t).sum(1), (~p & t).sum(1), (~p & ~t).sum(1)], dim=1).to(like.dtype)
         return mask, counts
 
-    def score(mask, target):
-        t = (target > 0).to(torch.uint8)
-        if surface is not None:
-            surface.append(metrics.surface_scores(mask, t))
-        if objects is not None:
-            objects.append(metrics.object_scores(mask, t, args.connectivity))
-        if obj_hd is not None:
-            obj_hd.append(metrics.object_hausdorff(mask, t, args.connectivity))
+    def label_maps(items):
+        return torch.cat([it[1].long().reshape(1, *it[0].shape[2:]) for it in items])
 
-    # forward + the device-side counts as ONE replayed hipGraph per image shape (medt_amd.trainer.InferStep): an eager
-    # forward is ~110 dependent launches issued from Python and is host-bound
-    infer = InferStep(model)
-    # The reference's loop runs ONE image per forward (test.py:106-119, batch size 1).  One replay costs the local branch's
-    # dependent chain whatever the batch (0.8 ms for one image, 0.74 ms for four: bench.py's fwd_ms_per_image_bs1 / fwd_ms_per_image),
-    # and in eval mode the images of a batch do not interact -- so --gather loader items of the same shape share a replay.  The
-    # last, shorter batch is padded with copies of its last image (same graph; the padding's outputs are dropped).
-    def run(items):
-        xs = torch.cat([it[0] for it in items] + [items[-1][0]] * (gather - len(items))).to(device)
-        ys = torch.cat([it[1].long().reshape(1, *it[0].shape[2:]) for it in items] + [items[-1][1].long().reshape(1, *items[-1][0].shape[2:])] * (gather - len(items))).to(device)
-        if tta_infer is not None:      # the views of the batch, `gather` per replay; logits and counts of their mean
-            y_out, _, counts = tta_infer(xs[:len(items)], ys[:len(items)])
-        else:
-            y_out, counts = infer(xs, ys)
-        if cleaning:
-            mask, cleaned = clean((y_out[:len(items), 1] >= 0.5).to(torch.uint8) * 255, ys[:len(items)], counts)
-            scores.append(cleaned)
-            score(mask, ys[:len(items)])
-            mask = mask.cpu().numpy()
-            for k, it in enumerate(items):
-                imwrite(fulldir + it[2], mask[k])
-            return
-        scores.append(counts[:len(items)].clone())
-        if scoring:   # the mask the PNG holds (same comparison, on the device) against target > 0
-            score((y_out[:len(items), 1] >= 0.5).to(torch.uint8) * 255, ys[:len(items)])
-        yHaT = (y_out[:len(items)].detach().cpu().numpy() >= 0.5).astype(np.uint8) * 255
-        for k, it in enumerate(items):
-            imwrite(fulldir + it[2], yHaT[k, 1, :, :])
+    def to_mask(logits):
+        return (logits[:, 1] >= 0.5).to(torch.uint8) * 255
 
-    gather = max(1, args.gather)
-    pending = []
-    tta_infer = None
-    if args.tta != "off" and args.window != "on":
-        from medt_amd.tta import TtaInfer
-        tta_infer = TtaInfer(model, args.tta, gather=gather)
+    # One predictor: items (of group_items) -> the uint8 {0,255} mask (n,H,W) on the device, its (n,4) counts, the int64 label
+    # maps (n,H,W) on the device.  Each runs forward + counts as replayed hipGraphs (medt_amd.trainer.InferStep): an eager
+    # forward is ~110 dependent launches issued from Python and is host-bound.
     if args.window == "on":
         # every loader item may have its own H x W: one image at a time, its windows `gather` per replay; the PNG has the
         # image's size and the counts are those of the whole image
         from medt_amd.window import WindowInfer
         winfer = WindowInfer(model, args.imgsize, gather=gather, stride=args.window_stride,
                              tta=None if args.tta == "off" else args.tta)
-        for batch_idx, (X_batch, y_batch, *rest) in enumerate(valloader):
-            image_filename = rest[0][0] if isinstance(rest[0][0], str) else '%s.png' % str(batch_idx + 1).zfill(3)
-            target = y_batch.long().reshape(1, *X_batch.shape[2:]).to(device)
-            _, mask, counts = winfer(X_batch.to(device), target)
-            if cleaning:
-                mask, counts = clean(mask.unsqueeze(0), target, counts)
-                mask = mask[0]
-            scores.append(counts)
-            if scoring:
-                score(mask.unsqueeze(0), target)
-            imwrite(fulldir + image_filename, mask.cpu().numpy())
-        valloader = ()
-    for batch_idx, (X_batch, y_batch, *rest) in enumerate(valloader):
-        image_filename = rest[0][0] if isinstance(rest[0][0], str) else '%s.png' % str(batch_idx + 1).zfill(3)
-        if pending and pending[0][0].shape != X_batch.shape:
-            run(pending)
-            pending = []
-        pending.append((X_batch, y_batch, image_filename))
-        if len(pending) == gather:
-            run(pending)
-            pending = []
-    if pending:
-        run(pending)
+
+        def predict(items):
+            target = label_maps(items).to(device)
+            _, mask, counts = winfer(items[0][0].to(device), target)
+            return mask.unsqueeze(0), counts, target
+    elif args.tta != "off":
+        from medt_amd.tta import TtaInfer
+        tta_infer = TtaInfer(model, args.tta, gather=gather)
+
+        def predict(items):        # the views of the group, `gather` per replay; mask and counts of their mean
+            target = label_maps(items).to(device)
+            merged, _, counts = tta_infer(torch.cat([it[0] for it in items]).to(device), target)
+            return to_mask(merged), counts, target
+    else:
+        # The reference's loop runs ONE image per forward (test.py:106-119, batch size 1).  One replay costs the local branch's
+        # dependent chain whatever the batch (0.8 ms for one image, 0.74 ms for four: bench.py's fwd_ms_per_image_bs1 /
+        # fwd_ms_per_image), and in eval mode the images of a batch do not interact -- so a group shares a replay, the counts
+        # inside it.  A shorter group is padded with copies of its last image (same graph; the padding's outputs are dropped).
+        infer = InferStep(model)
+
+        def predict(items):
+            n, shape = len(items), items[0][0].shape
+            xs = padded_batch(n, gather, shape[1:], device)
+            ys = padded_batch(n, gather, shape[2:], device, torch.int64)
+            xs[:n].copy_(torch.cat([it[0] for it in items]))
+            ys[:n].copy_(label_maps(items))
+            logits, counts = run_padded(infer, xs, n, gather, ys)
+            return to_mask(logits), counts, ys[:n]
+
+    for items in group_items(valloader, 1 if args.window == "on" else gather):
+        mask, counts, target = predict(items)
+        if args.fill_holes == "on" or args.min_object > 0:
+            mask, counts = clean(mask, target, counts)
+        scores.append(counts)
+        if scored:                 # the mask the PNG holds against target > 0
+            t = (target > 0).to(torch.uint8)
+            for (_, metric, _, _), batches in scored:
+                batches.append(metric(mask, t, args.connectivity))
+        mask = mask.cpu().numpy()
+        for k, it in enumerate(items):
+            imwrite(fulldir + it[2], mask[k])
     if scores:
-        f1, iou, pa = metrics.segmentation_scores(torch.cat(scores))
-        print("images {}  F1 {:.4f}  mIoU {:.4f}  PA {:.4f}".format(len(f1), f1.mean().item(), iou.mean().item(),
-                                                                   pa.mean().item()))
-    if surface:
-        valid = torch.cat([s["valid"] for s in surface])
-        hd, hd95, assd = (torch.cat([s[k] for s in surface])[valid] for k in ("hd", "hd95", "assd"))
-        print("surface images {}/{}  HD {:.4f}  HD95 {:.4f}  ASSD {:.4f}".format(
-            int(valid.sum()), len(valid), *(v.mean().item() if len(v) else float("nan") for v in (hd, hd95, assd))))
-    if objects:
-        valid = torch.cat([s["valid"] for s in objects])
-        f1o, diceo, aji, pq = (torch.cat([s[k] for s in objects])[valid] for k in ("f1", "dice", "aji", "pq"))
-        print("objects images {}/{}  F1obj {:.4f}  Diceobj {:.4f}  AJI {:.4f}  PQ {:.4f}".format(
-            int(valid.sum()), len(valid), *(v.mean().item() if len(v) else float("nan") for v in (f1o, diceo, aji, pq))))
-    if obj_hd:
-        valid = torch.cat([s["valid"] for s in obj_hd])
-        hobj = torch.cat([s["hd"] for s in obj_hd])[valid]
-        print("object hausdorff images {}/{}  Hobj {:.4f}".format(int(valid.sum()), len(valid),
-                                                                  hobj.mean().item() if len(hobj) else float("nan")))
+        print(images_line(torch.cat(scores)))
+        for (prefix, _, keys, labels), batches in scored:
+            print(summary_line(prefix, keys, labels, batches))
 
 
 if __name__ == "__main__":

@@ -36,7 +36,7 @@ from torch.utils.data import DataLoader
 import lib
 from metrics import BorderLoss, BoundaryLoss, DiceCELoss, LogNLLLoss
 from medt_amd import dp
-from medt_amd.data import DevicePrefetcher, imwrite, make_synthetic_dataset
+from medt_amd.data import DevicePrefetcher, imwrite, item_filename, make_synthetic_dataset
 from medt_amd.optim import FlatAdam
 from medt_amd.trainer import InferStep, TrainStep
 
@@ -259,7 +259,7 @@ def main():
             fulldir = direc + "/{}/".format(epoch)
             os.makedirs(fulldir, exist_ok=True)
             for batch_idx, (X_batch, y_batch, *rest) in enumerate(valloader):
-                image_filename = rest[0][0] if isinstance(rest[0][0], str) else '%s.png' % str(batch_idx + 1).zfill(3)
+                image_filename = item_filename(rest, batch_idx)
                 # the model stays in train mode here, as in the reference (:174-184): batch statistics, and every forward
                 # updates the running statistics; replayed as one hipGraph per image shape (InferStep)
                 y_out = infer_step(X_batch.to(device))

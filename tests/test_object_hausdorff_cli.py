@@ -10,9 +10,9 @@ import torch
 
 import helpers as H  # noqa: F401
 import hausdorff_oracle as HO
-from test_label_cli import _objects_line, _png
+from test_label_cli import _objects_line, _pixel_line, _png
 from test_label_gpu import _dev
-from test_surface_cli import _checkpoint, _dataset, _run
+from test_surface_cli import _checkpoint, _dataset, _oracle_line, _run
 
 pytestmark = pytest.mark.gpu
 
@@ -59,6 +59,31 @@ def test_cli_object_hausdorff_on_and_off(plain, device, emulating):
     assert len(files) == 3 and sorted(os.listdir(root / "off")) == files
     for f in files:
         assert (root / "off" / f).read_bytes() == (plain["dir"] / f).read_bytes() == (root / "on" / f).read_bytes(), f
+
+
+ALL_STAGES = ("--fill_holes", "on", "--min_object", "6", "--surface", "on", "--objects", "on", "--object_hausdorff", "on")
+
+
+def test_cli_every_stage_at_once_behind_each_view_predictor(tmp_path, device, emulating, plain):
+    """Every stage of test.py's one loop switched on -- both clean-ups and the three score lines -- behind --tta flips, behind
+    --tta d4 at a gather that divides neither the group nor its views, and behind --window on --tta d4 on 40 x 52 images: each of
+    the four printed lines is the oracle's, computed from the PNGs the run wrote, and no image is counted out.  The emulated
+    device runs only the first of the three (the three together take it ten minutes); the GPU runs all."""
+    wide = _dataset(str(tmp_path / "data"), 2, (40, 52), 50)
+    runs = [("flips", plain["data"], 3, ("--tta", "flips")),
+            ("d4", plain["data"], 3, ("--tta", "d4", "--gather", "3")),
+            ("win_d4", wide, 2, ("--window", "on", "--tta", "d4"))]
+    for name, data, n, flags in runs[:1] if emulating else runs:
+        out_dir = str(tmp_path / name)
+        out = _run(emulating, plain["ckpt"], data, out_dir, *flags, *ALL_STAGES)
+        print(out)
+        lines = out.strip().splitlines()
+        assert lines[-4:] == [_pixel_line(data, out_dir), _oracle_line(data, out_dir), _objects_line(data, out_dir),
+                              _hausdorff_line(data, out_dir)], (name, out)
+        assert lines[-4].startswith("images {}  F1 ".format(n)), (name, out)
+        for line, prefix in zip(lines[-3:], ("surface", "objects", "object hausdorff")):
+            assert line.startswith("{} images {}/{}  ".format(prefix, n, n)), (name, line)
+        assert len(os.listdir(out_dir)) == n
 
 
 def test_cli_object_hausdorff_with_windows_objects_and_clean_ups(tmp_path, device, emulating, plain):
