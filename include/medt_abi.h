@@ -41,7 +41,8 @@ extern "C" {
  * number: additions only, nothing that version 11 declared was removed or changed, so a caller built against the earlier
  * header keeps working.  medt_label_boxes and medt_pair_hausdorff were added under the same number, in the same way.
  * medt_signed_edt and the medt_boundary_* entry points were added under the same number, in the same way.  medt_object_edt2
- * and the medt_border_* entry points were added under the same number, in the same way. */
+ * and the medt_border_* entry points were added under the same number, in the same way.  medt_augment_warp was added under
+ * the same number, in the same way. */
 #define MEDT_ABI_VERSION 11
 
 #define MEDT_OK            0
@@ -446,7 +447,7 @@ int medt_tta_merge(const float* view_logits, float* merged, uint8_t* mask, uint8
  *   [0] cy [1] cx  crop origin    [2] flip (!= 0)    [3] identity (!= 0: the affine step is skipped, no float round trip)
  *   [4..9] m00 m01 m02 m10 m11 m12   the INVERSE affine map, output pixel centre -> cropped image
  *   [10..13] operation of jitter slot k: 0 none, 1 brightness, 2 contrast, 3 saturation, 4 hue    [14..17] its factor
- *   [18..19] reserved, 0
+ *   [18] elastic (medt_augment_warp, below; medt_augment_apply ignores it)    [19] reserved, 0
  * Output pixel (i, j): fx = m00 (j+.5) + m01 (i+.5) + m02, fy = m10 (j+.5) + m11 (i+.5) + m12, sx = floor(fx), sy = floor(fy)
  * (PIL's Image.transform(AFFINE, NEAREST)).  Outside [0,tw) x [0,th) -- tested on the floats, so non-finite or huge
  * coordinates are outside -- the image receives 0.0 and the mask 0, neither jittered.  Flip: sx -> tw-1-sx.  Source pixel
@@ -468,6 +469,27 @@ int medt_augment_stats(const uint8_t* image, const float* params, float* workspa
                        int tw, void* stream);
 int medt_augment_apply(const uint8_t* image, const uint8_t* mask, const float* params, float* workspace, float* out_image,
                        int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, void* stream);
+
+/* Elastic deformation inside the joint augmentation (U-Net's random displacement vectors on a coarse grid; not in the
+ * reference): medt_augment_warp is medt_augment_apply with a cubic B-spline free-form deformation of the records whose slot
+ *   [18] elastic (!= 0)      ([19] stays reserved, 0; a record keeps medt_augment_param_floats() == 20 floats)
+ * is set.  field: a DEVICE table (N,2,G+3,G+3) float32, the control lattice of G x G cells per image in pixels, channel 0 =
+ * dx, channel 1 = dy, 1 <= G <= 8.  Output pixel (i, j) of a th x tw crop whose record has the flag:
+ *   tx = (j+.5) G / tw, cx = min(floor(tx), G-1), u = tx - cx;   ty, cy, v likewise from i and th
+ *   B0 = (1-u)^3/6, B1 = (3u^3-6u^2+4)/6, B2 = (-3u^3+3u^2+3u+1)/6, B3 = u^3/6        (non-negative, sum 1)
+ *   d = sum_a B_a(v) (sum_b B_b(u) field[.][cy+a][cx+b])      summed b ascending inside, a ascending outside
+ *   p = (j+.5+dx, i+.5+dy);  f = M p with the record's inverse affine map, f = p under the identity flag
+ *   inside: 0 <= fx < tw and 0 <= fy < th on the floats (NaN and huge coordinates are outside); outside, image 0, class 0
+ *   mask: nearest, floor(f).  image: bilinear about the pixel centres, ux = fx-.5, x0 = floor(ux), wx = ux-x0, taps x0 and
+ *   x0+1, likewise in y; tap indices are clamped to [0,tw-1] x [0,th-1] of the (flipped) crop, mirrored when flip, offset by
+ *   the crop origin and clamped to the input.  Every tap is u8/255 and runs through the record's jitter slots BEFORE the
+ *   blend (1-wy)((1-wx) t00 + wx t01) + wy((1-wx) t10 + wx t11); mean_g is medt_augment_stats' mean of the unwarped crop.
+ * A record without the flag gets medt_augment_apply's nearest path and its bits, whatever the other records of the batch
+ * hold; a set flag with an all-zero lattice and the identity flag gives those bits too (the weights are exactly 0 and 1).
+ * Lattice indices are clamped to [0,G+2]: no table makes a read leave its buffer.  No atomics, the same bits on every run.
+ * Refusals: those of medt_augment_apply, a NULL field, G outside 1..8 (MEDT_EINVAL). */
+int medt_augment_warp(const uint8_t* image, const uint8_t* mask, const float* params, const float* field, int G, float* workspace,
+                      float* out_image, int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, void* stream);
 
 /* Exact squared Euclidean distance transform of binary masks on the device, in two passes -- the building block of the
  * surface-distance scores (metrics.surface_scores: Hausdorff distance, its 95th percentile, average symmetric surface

@@ -1621,6 +1621,254 @@ int augment_apply(const uint8_t* image, const uint8_t* mask, const float* params
 }
 
 // --------------------------------------------------------------------------- //
+// Elastic deformation inside the joint augmentation (U-Net's "random displacement vectors on a coarse grid"; not in the
+// reference): record slot [18] != 0 gives the image a cubic B-spline free-form deformation over G x G cells, 1 <= G <= 8.
+// field (N,2,G+3,G+3) float32 is the control lattice in pixels, channel 0 = dx, channel 1 = dy, a DEVICE table.
+// Output pixel (i, j) of a flagged record:
+//   tx = (j+.5) G / tw, cx = min(floor(tx), G-1), u = tx - cx;  ty, cy, v likewise from i, th
+//   B0 = (1-u)^3/6, B1 = (3u^3-6u^2+4)/6, B2 = (-3u^3+3u^2+3u+1)/6, B3 = u^3/6      (>= 0, sum 1)
+//   d = sum_a B_a(v) (sum_b B_b(u) field[.][cy+a][cx+b]), b ascending inside, a ascending outside
+//   p = (j+.5+dx, i+.5+dy);  f = M p, or p when the record has the identity flag;  inside as in augment_apply
+//   mask: nearest, floor(f).  image: bilinear about pixel centres, ux = fx-.5, x0 = floor(ux), wx = ux-x0, taps x0, x0+1
+//   clamped to the crop, mirrored when flipped, offset by the origin and clamped to the input; every tap is u8/255 and runs
+//   through the jitter slots BEFORE the blend (1-wy)((1-wx) t00 + wx t01) + wy((1-wx) t10 + wx t11).
+// A zero lattice under the identity flag has wx = wy = 0 exactly: the bits of augment_apply -- as long as aug_jitter, which is
+// compiled with the default contraction, is contracted here as it is there: the tap loop therefore holds the 4 pixels in the
+// shape augment_apply_kernel has them.  A record without the flag takes augment_apply's body (the flag is
+// uniform over a block).  The spline, the map and the weights are evaluated without
+// contraction, operation for operation as written, so the float32 restatement in tests/elastic_oracle.py follows them.
+// Lattice indices are clamped to [0, G+2], tap indices as above: no table, finite or not, makes a read leave its buffer.
+// --------------------------------------------------------------------------- //
+constexpr int AUG_ELASTIC = 18, AUG_GMAX = 8, AUG_LMAX = AUG_GMAX + 3;
+
+// the four cubic B-spline weights at u in [0, 1]
+__device__ __forceinline__ void aug_bspline(float u, float (&B)[4]) {
+#pragma clang fp contract(off)
+    const float om = 1.f - u, u2 = u * u, u3 = u2 * u;
+    B[0] = om * om * om / 6.f;
+    B[1] = (3.f * u3 - 6.f * u2 + 4.f) / 6.f;
+    B[2] = (-3.f * u3 + 3.f * u2 + 3.f * u + 1.f) / 6.f;
+    B[3] = u3 / 6.f;
+}
+
+// cell and weights of output coordinate k of `extent` under a grid of G cells
+__device__ __forceinline__ int aug_cell(int k, int extent, int G, float (&B)[4]) {
+#pragma clang fp contract(off)
+    const float t = (k + 0.5f) * (float)G / (float)extent;
+    const int c = min(max((int)floorf(t), 0), G - 1);
+    aug_bspline(t - (float)c, B);
+    return c;
+}
+
+// the 4 pixels of a work-item to both outputs, as augment_apply_kernel stores them
+template <int C, bool VEC4>
+__device__ __forceinline__ void aug_store(const float (&v)[4][C], const int64_t (&lab)[4], float* __restrict__ out_image,
+                                          int64_t* __restrict__ out_mask, int n, int i, int j0, int th, int tw) {
+    int64_t* ml = out_mask + ((size_t)n * th + i) * tw + j0;
+    if (VEC4) {
+        AugLabel2 l01, l23;
+        l01.a = lab[0]; l01.b = lab[1]; l23.a = lab[2]; l23.b = lab[3];
+        reinterpret_cast<AugLabel2*>(ml)[0] = l01;
+        reinterpret_cast<AugLabel2*>(ml)[1] = l23;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (j0 + e < tw) ml[e] = lab[e];
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        float* dst = out_image + (((size_t)n * C + c) * th + i) * tw + j0;
+        if (VEC4) {
+            *reinterpret_cast<float4*>(dst) = make_float4(v[0][c], v[1][c], v[2][c], v[3][c]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (j0 + e < tw) dst[e] = v[e][c];
+        }
+    }
+}
+
+// a work-item: 4 consecutive output x of one row of image blockIdx.y, all channels, like augment_apply_kernel
+template <int C, bool VEC4>
+__global__ __launch_bounds__(MEDT_THREADS) void augment_warp_kernel(const uint8_t* __restrict__ image,
+                                                                    const uint8_t* __restrict__ mask,
+                                                                    const float* __restrict__ params,
+                                                                    const float* __restrict__ field, int G,
+                                                                    const float* __restrict__ partials,
+                                                                    float* __restrict__ means,
+                                                                    float* __restrict__ out_image,
+                                                                    int64_t* __restrict__ out_mask, int H, int W, int th,
+                                                                    int tw, int parts, int items) {
+    MEDT_STATIC_SHARED float lat[2 * AUG_LMAX * AUG_LMAX];
+    const int n = blockIdx.y;
+    const float* rec = params + (size_t)n * AUG_P;
+    const AugCrop o = aug_origin(rec, H, W);
+    const bool flip = rec[AUG_FLIP] != 0.f, ident = rec[AUG_IDENT] != 0.f, elastic = rec[AUG_ELASTIC] != 0.f;
+    const float m00 = rec[AUG_M], m01 = rec[AUG_M + 1], m02 = rec[AUG_M + 2], m10 = rec[AUG_M + 3], m11 = rec[AUG_M + 4],
+                m12 = rec[AUG_M + 5];
+    float mean_g = 0.f;
+    if (partials) {
+        double s = 0.0;
+        for (int p = 0; p < parts; ++p) s += (double)partials[(size_t)n * parts + p];
+        mean_g = (float)(s / (double)((size_t)th * tw));
+    }
+    if (means && blockIdx.x == 0 && threadIdx.x == 0) means[n] = mean_g;
+    const int tw4 = (tw + 3) >> 2, L = G + 3, LL = L * L;
+    if (!elastic) {                        // uniform over the block: augment_apply_kernel's body
+        for (int it = blockIdx.x * MEDT_THREADS + threadIdx.x; it < items; it += gridDim.x * MEDT_THREADS) {
+            const int i = it / tw4, j0 = (it - i * tw4) * 4;
+            float v[4][C];
+            int64_t lab[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int j = j0 + e;
+                int sx = j, sy = i;
+                bool inside = VEC4 || j < tw;
+                if (!ident) {
+                    const float fx = m00 * (j + 0.5f) + m01 * (i + 0.5f) + m02, fy = m10 * (j + 0.5f) + m11 * (i + 0.5f) + m12;
+                    inside = inside && fx >= 0.f && fx < (float)tw && fy >= 0.f && fy < (float)th;      // false for NaN
+                    sx = inside ? (int)floorf(fx) : 0;
+                    sy = inside ? (int)floorf(fy) : 0;
+                }
+                if (flip) sx = tw - 1 - sx;
+                const int y = min(max(o.cy + sy, 0), H - 1), x = min(max(o.cx + sx, 0), W - 1);
+                const size_t px = ((size_t)n * H + y) * W + x;
+                lab[e] = 0;
+#pragma unroll
+                for (int c = 0; c < C; ++c) v[e][c] = 0.f;
+                if (inside) {
+                    lab[e] = (int64_t)mask[px];
+#pragma unroll
+                    for (int c = 0; c < C; ++c) v[e][c] = (float)image[px * C + c] / 255.f;
+                    aug_jitter<C, false>(v[e], rec, mean_g);
+                }
+            }
+            aug_store<C, VEC4>(v, lab, out_image, out_mask, n, i, j0, th, tw);
+        }
+    } else {
+        for (int k = threadIdx.x; k < 2 * LL; k += MEDT_THREADS) lat[k] = field[(size_t)n * 2 * LL + k];      // once per block
+        __syncthreads();
+        const float e00 = ident ? 1.f : m00, e01 = ident ? 0.f : m01, e02 = ident ? 0.f : m02, e10 = ident ? 0.f : m10,
+                    e11 = ident ? 1.f : m11, e12 = ident ? 0.f : m12;
+        const uint8_t* mask_n = mask + (size_t)n * H * W;
+        for (int it = blockIdx.x * MEDT_THREADS + threadIdx.x; it < items; it += gridDim.x * MEDT_THREADS) {
+            const int i = it / tw4, j0 = (it - i * tw4) * 4;
+            float v[4][C];
+            int64_t lab[4];
+            float fx[4], fy[4];
+            {                                                   // the geometry of the 4 pixels: spline, map
+#pragma clang fp contract(off)
+                float Bv[4];
+                const int cy = aug_cell(i, th, G, Bv);          // row-uniform
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float Bu[4];
+                    const int cx = aug_cell(j0 + e, tw, G, Bu);
+                    float d[2];
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        float acc = 0.f;
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) {
+                            const float* row = lat + k * LL + min(max(cy + a, 0), L - 1) * L;
+                            float s = 0.f;
+#pragma unroll
+                            for (int b = 0; b < 4; ++b) s = s + Bu[b] * row[min(max(cx + b, 0), L - 1)];
+                            acc = acc + Bv[a] * s;
+                        }
+                        d[k] = acc;
+                    }
+                    const float px = (j0 + e + 0.5f) + d[0], py = (i + 0.5f) + d[1];
+                    fx[e] = e00 * px + e01 * py + e02;          // (the identity flag: 1 px + 0 py + 0, px itself or NaN)
+                    fy[e] = e10 * px + e11 * py + e12;
+                }
+            }
+            bool inside[4];
+            float wx[4], wy[4];
+            int x0[4], y0[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {                       // the mask tap, the image taps' corner and weights
+                inside[e] = (VEC4 || j0 + e < tw) && fx[e] >= 0.f && fx[e] < (float)tw && fy[e] >= 0.f && fy[e] < (float)th;   // false for NaN
+                lab[e] = 0;
+                wx[e] = wy[e] = 0.f;
+                x0[e] = y0[e] = 0;
+#pragma unroll
+                for (int c = 0; c < C; ++c) v[e][c] = 0.f;
+                if (inside[e]) {
+#pragma clang fp contract(off)
+                    int sx = (int)floorf(fx[e]);
+                    const int sy = (int)floorf(fy[e]);
+                    if (flip) sx = tw - 1 - sx;
+                    const int my = min(max(o.cy + sy, 0), H - 1), mx = min(max(o.cx + sx, 0), W - 1);
+                    lab[e] = (int64_t)mask_n[(size_t)my * W + mx];
+                    const float ux = fx[e] - 0.5f, uy = fy[e] - 0.5f, fx0 = floorf(ux), fy0 = floorf(uy);
+                    wx[e] = ux - fx0; wy[e] = uy - fy0;
+                    x0[e] = (int)fx0; y0[e] = (int)fy0;
+                }
+            }
+            float r[4][C];
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int c = 0; c < C; ++c) r[e][c] = 0.f;
+#pragma unroll 1
+            for (int tap = 0; tap < 4; ++tap) {                 // one tap at a time: fetch as bytes, jitter, blend
+                const bool right = tap & 1, lower = tap >> 1;
+                asm volatile("" ::: "memory");                  // the record is re-read per tap, where the jitter uses it (below)
+                float t[4][C];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {                   // the 4 pixels side by side, as augment_apply_kernel has them
+                    int sx = min(max(x0[e] + (int)right, 0), tw - 1);
+                    const int sy = min(max(y0[e] + (int)lower, 0), th - 1);
+                    if (flip) sx = tw - 1 - sx;
+                    const int y = min(max(o.cy + sy, 0), H - 1), x = min(max(o.cx + sx, 0), W - 1);
+                    const size_t px = ((size_t)n * H + y) * W + x;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) t[e][c] = 0.f;
+                    if (inside[e]) {
+#pragma unroll
+                        for (int c = 0; c < C; ++c) t[e][c] = (float)image[px * C + c] / 255.f;
+                        aug_jitter<C, false>(t[e], rec, mean_g);
+                    }
+                }
+                {
+#pragma clang fp contract(off)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float wxk = right ? wx[e] : 1.f - wx[e], wyk = lower ? wy[e] : 1.f - wy[e];
+#pragma unroll
+                        for (int c = 0; c < C; ++c) {
+                            r[e][c] = right ? r[e][c] + wxk * t[e][c] : wxk * t[e][c];
+                            if (right) v[e][c] = lower ? v[e][c] + wyk * r[e][c] : wyk * r[e][c];
+                        }
+                    }
+                }
+            }
+            aug_store<C, VEC4>(v, lab, out_image, out_mask, n, i, j0, th, tw);
+        }
+    }
+}
+
+int augment_warp(const uint8_t* image, const uint8_t* mask, const float* params, const float* field, int G, float* workspace,
+                 float* out_image, int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, hipStream_t s) {
+    const int parts = augment_parts(th, tw), items = th * ((tw + 3) / 4);
+    const float* partials = (workspace && use_stats) ? workspace : nullptr;
+    float* means = workspace ? workspace + (size_t)N * parts : nullptr;
+    const dim3 grid((unsigned)min((items + MEDT_THREADS - 1) / MEDT_THREADS, 1024), N), block(MEDT_THREADS);
+    const bool vec = (tw % 4 == 0) && ((uintptr_t)out_image % 16 == 0) && ((uintptr_t)out_mask % 16 == 0);
+#define MEDT_AUG_LAUNCH(CC, VV)                                                                                          \
+    hipLaunchKernelGGL((augment_warp_kernel<CC, VV>), grid, block, 0, s, image, mask, params, field, G, partials, means, \
+                       out_image, out_mask, H, W, th, tw, parts, items)
+    if (C == 3) {
+        if (vec) MEDT_AUG_LAUNCH(3, true); else MEDT_AUG_LAUNCH(3, false);
+    } else {
+        if (vec) MEDT_AUG_LAUNCH(1, true); else MEDT_AUG_LAUNCH(1, false);
+    }
+#undef MEDT_AUG_LAUNCH
+    return launch_status("augment_warp");
+}
+
+// --------------------------------------------------------------------------- //
 // Exact squared Euclidean distance transform of uint8 masks (N,H,W) -> int32 (N,H,W), for the surface-distance scores
 // (metrics.surface_scores: Hausdorff distance, its 95th percentile, average symmetric surface distance; not in the reference).
 //   d2[y,x] = min over the feature pixels (y',x') of (y-y')^2 + (x-x')^2      MEDT_EDT_NONE where the image has none

@@ -1112,20 +1112,40 @@ int medt_augment_stats(const uint8_t* image, const float* params, float* workspa
     return augment_stats(image, params, workspace, N, H, W, C, th, tw, (hipStream_t)stream);
 }
 
-int medt_augment_apply(const uint8_t* image, const uint8_t* mask, const float* params, float* workspace, float* out_image,
-                       int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, void* stream) {
-    if (!augment_geometry_ok("augment_apply", N, H, W, C, th, tw)) return MEDT_EINVAL;
+// the refusals medt_augment_apply and medt_augment_warp share
+static int augment_apply_args(const char* what, const uint8_t* image, const uint8_t* mask, const float* params,
+                              const float* workspace, const float* out_image, const int64_t* out_mask, int N, int H, int W, int C,
+                              int th, int tw, int use_stats) {
+    if (!augment_geometry_ok(what, N, H, W, C, th, tw)) return MEDT_EINVAL;
     if (!image || !mask || !params || !out_image || !out_mask) {
-        set_error("augment_apply: null image, mask, parameter table or output"); return MEDT_EINVAL;
+        set_error("%s: null image, mask, parameter table or output", what); return MEDT_EINVAL;
     }
     if (use_stats && !workspace) {
-        set_error("augment_apply: use_stats without the workspace medt_augment_stats filled"); return MEDT_EINVAL;
+        set_error("%s: use_stats without the workspace medt_augment_stats filled", what); return MEDT_EINVAL;
     }
     if ((size_t)N * H * W * C >= ((size_t)1 << 31) || (size_t)N * C * th * tw >= ((size_t)1 << 31)) {
-        set_error("augment_apply: %d images of %d x %d x %d -> %d x %d: 2^31 elements or more", N, H, W, C, th, tw);
+        set_error("%s: %d images of %d x %d x %d -> %d x %d: 2^31 elements or more", what, N, H, W, C, th, tw);
         return MEDT_EUNSUPPORTED;
     }
+    return MEDT_OK;
+}
+
+int medt_augment_apply(const uint8_t* image, const uint8_t* mask, const float* params, float* workspace, float* out_image,
+                       int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, void* stream) {
+    if (int rc = augment_apply_args("augment_apply", image, mask, params, workspace, out_image, out_mask, N, H, W, C, th, tw, use_stats))
+        return rc;
     return augment_apply(image, mask, params, workspace, out_image, out_mask, N, H, W, C, th, tw, use_stats, (hipStream_t)stream);
+}
+
+int medt_augment_warp(const uint8_t* image, const uint8_t* mask, const float* params, const float* field, int G, float* workspace,
+                      float* out_image, int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, void* stream) {
+    if (int rc = augment_apply_args("augment_warp", image, mask, params, workspace, out_image, out_mask, N, H, W, C, th, tw, use_stats))
+        return rc;
+    if (!field || G < 1 || G > 8) {
+        set_error("augment_warp: null lattice or a grid of %d cells (1 .. 8 expected)", G); return MEDT_EINVAL;
+    }
+    return augment_warp(image, mask, params, field, G, workspace, out_image, out_mask, N, H, W, C, th, tw, use_stats,
+                        (hipStream_t)stream);
 }
 
 static int edt_geometry(const char* what, int N, int H, int W) {

@@ -133,6 +133,9 @@ int augment_stats(const uint8_t* image, const float* params, float* workspace, i
                   hipStream_t s);
 int augment_apply(const uint8_t* image, const uint8_t* mask, const float* params, float* workspace, float* out_image,
                   int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, hipStream_t s);
+// augment_apply with the elastic deformation of the records whose slot [18] is set: field (N,2,G+3,G+3), 1 <= G <= 8
+int augment_warp(const uint8_t* image, const uint8_t* mask, const float* params, const float* field, int G, float* workspace,
+                 float* out_image, int64_t* out_mask, int N, int H, int W, int C, int th, int tw, int use_stats, hipStream_t s);
 // exact squared Euclidean distance transform in two passes (medt_abi.h): columns (of the mask, or of its border), then rows
 int edt_cols(const uint8_t* mask, int32_t* g2, int N, int H, int W, int border_mode, hipStream_t s);
 int edt_rows(const int32_t* g2, const uint8_t* select, int32_t* d2, int N, int H, int W, hipStream_t s);

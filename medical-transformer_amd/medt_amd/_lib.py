@@ -160,6 +160,7 @@ SIGNATURES = {
     "medt_augment_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "medt_augment_stats": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p]),
     "medt_augment_apply": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p]),
+    "medt_augment_warp": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p]),
     "medt_edt_cols": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     "medt_edt_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
     "medt_signed_edt": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),

@@ -1,6 +1,7 @@
 """Joint augmentation on the device: random crop, horizontal flip, colour jitter (image only) and a random affine map (image
 and mask), in the order of the reference's JointTransform2D.__call__ (utils.py:70-98), which does them per item with
-torchvision on the host.
+torchvision on the host -- and, not in the reference, U-Net's elastic deformation: a cubic B-spline free-form deformation
+over a coarse grid of random displacements (`draw_field`), applied in front of the affine map, the image sampled bilinearly.
 
 The host only DRAWS: `draw_record` turns the random numbers of one item into a record of `ops.augment_param_floats()` floats
 (layout: include/medt_abi.h), `RawJointTransform2D` hands the dataset's decoded uint8 image and mask on untouched together
@@ -23,6 +24,8 @@ from . import ops
 
 PARAM_FLOATS = 20                     # == ops.augment_param_floats() (checked by DeviceAugment and the tests)
 OP_NONE, OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION, OP_HUE = 0, 1, 2, 3, 4
+ELASTIC_SLOT = 18                     # != 0: the record's image gets the elastic deformation (include/medt_abi.h)
+ELASTIC_MAX_GRID = 8
 
 
 def inverse_affine_matrix(center, angle, translate, scale, shear):
@@ -45,9 +48,10 @@ def inverse_affine_matrix(center, angle, translate, scale, shear):
     return m
 
 
-def make_record(cy=0, cx=0, flip=False, matrix=None, ops_and_factors=()):
+def make_record(cy=0, cx=0, flip=False, matrix=None, ops_and_factors=(), elastic=False):
     """One record as a float32 numpy array.  matrix: the six entries of the inverse map, or None for the identity flag;
-    ops_and_factors: up to four (operation code, factor) pairs in the order they apply."""
+    ops_and_factors: up to four (operation code, factor) pairs in the order they apply; elastic: slot 18, the image is
+    deformed by its control lattice (draw_field)."""
     if len(ops_and_factors) > 4:
         raise ValueError("a record holds at most four colour operations")
     r = np.zeros(PARAM_FLOATS, np.float32)
@@ -59,6 +63,7 @@ def make_record(cy=0, cx=0, flip=False, matrix=None, ops_and_factors=()):
         r[4:10] = matrix
     for k, (op, fac) in enumerate(ops_and_factors):
         r[10 + k], r[14 + k] = op, fac
+    r[ELASTIC_SLOT] = 1.0 if elastic else 0.0
     return r
 
 
@@ -96,6 +101,15 @@ def draw_record(h, w, crop, p_flip=0.5, jitter=None, p_affine=0.0):
     return make_record(cy, cx, flip, matrix, ops_and_factors)
 
 
+def draw_field(G, sigma):
+    """The control lattice of one elastic deformation over G x G cells: (2, G+3, G+3) float32 displacements in pixels
+    (channel 0 = dx, channel 1 = dy), normal with standard deviation sigma, clipped to +-3 sigma -- U-Net's random
+    displacement vectors on a coarse grid.  One np.random call."""
+    if not 1 <= G <= ELASTIC_MAX_GRID:
+        raise ValueError(f"an elastic grid of 1 .. {ELASTIC_MAX_GRID} cells per side expected, got {G}")
+    return np.clip(np.random.normal(0.0, sigma, (2, G + 3, G + 3)), -3.0 * sigma, 3.0 * sigma).astype(np.float32)
+
+
 def parse_jitter(text):
     """--aug_jitter "b,c,s,h": four non-negative ranges, hue at most 0.5 (ColorJitter's own limits)."""
     try:
@@ -111,10 +125,14 @@ def parse_jitter(text):
 
 class RawJointTransform2D:
     """Dataset transform of the device path: (image, mask) -> (uint8 HWC image, uint8 HW mask, float32 record).  The draws
-    happen here, per item, where data.JointTransform2D makes them; nothing is cropped, flipped or converted on the host."""
+    happen here, per item, where data.JointTransform2D makes them; nothing is cropped, flipped or converted on the host.
+    elastic = {"p", "grid", "sigma"}: a fourth element, the item's (2, grid+3, grid+3) control lattice -- drawn with
+    probability p AFTER every other draw of the item (the record's slot 18 says so), all zeros otherwise."""
 
-    def __init__(self, crop=None, p_flip=0.5, jitter=None, p_affine=0.0):
-        self.crop, self.p_flip, self.jitter, self.p_affine = crop, p_flip, jitter, p_affine
+    def __init__(self, crop=None, p_flip=0.5, jitter=None, p_affine=0.0, elastic=None):
+        self.crop, self.p_flip, self.jitter, self.p_affine, self.elastic = crop, p_flip, jitter, p_affine, elastic
+        if elastic is not None and not 1 <= int(elastic["grid"]) <= ELASTIC_MAX_GRID:
+            raise ValueError(f"an elastic grid of 1 .. {ELASTIC_MAX_GRID} cells per side expected, got {elastic['grid']}")
 
     def __call__(self, image, mask):
         image, mask = np.asarray(image), np.asarray(mask)
@@ -122,8 +140,15 @@ class RawJointTransform2D:
             image = image[:, :, None]
         h, w = image.shape[:2]
         rec = draw_record(h, w, self.crop, self.p_flip, self.jitter, self.p_affine)
-        return (torch.from_numpy(np.ascontiguousarray(image, np.uint8)),
+        item = (torch.from_numpy(np.ascontiguousarray(image, np.uint8)),
                 torch.from_numpy(np.ascontiguousarray(mask.reshape(h, w), np.uint8)), torch.from_numpy(rec))
+        if self.elastic is None:
+            return item
+        G = int(self.elastic["grid"])
+        if np.random.rand() < self.elastic["p"]:
+            rec[ELASTIC_SLOT] = 1.0
+            return item + (torch.from_numpy(draw_field(G, self.elastic["sigma"])),)
+        return item + (torch.zeros((2, G + 3, G + 3), dtype=torch.float32),)
 
 
 class DeviceAugment:
@@ -140,11 +165,11 @@ class DeviceAugment:
         """The per-image grey means the last call's contrast operations used (0 when the batch had none)."""
         return self._ws[(N, tuple(size))][-N:]
 
-    def __call__(self, img_u8, mask_u8, params, host_params=None):
+    def __call__(self, img_u8, mask_u8, params, host_params=None, field=None):
         N, H, W = img_u8.shape[:3]
         size = tuple(self.crop) if self.crop else (H, W)
         key = (N, size)
         ws = self._ws.get(key)
         if ws is None:
             ws = self._ws[key] = torch.zeros(ops.augment_workspace(N, size), device=img_u8.device, dtype=torch.float32)
-        return ops.augment_batch(img_u8, mask_u8, params, size, workspace=ws, host_params=host_params)
+        return ops.augment_batch(img_u8, mask_u8, params, size, workspace=ws, host_params=host_params, field=field)

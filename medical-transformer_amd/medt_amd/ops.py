@@ -907,6 +907,8 @@ def tta_merge(view_logits, views, threshold=0.5, want_logits=True, want_mask=Tru
 # joint augmentation of uint8 batches (medt_amd.augment)
 # --------------------------------------------------------------------------- #
 AUG_CONTRAST = 2.0          # operation code of a contrast slot (include/medt_abi.h)
+AUG_ELASTIC_SLOT = 18       # record slot of the elastic flag
+AUG_ELASTIC_MAX_GRID = 8    # cells per side of the elastic deformation's grid, at most
 
 
 def augment_param_floats():
@@ -921,13 +923,16 @@ def augment_workspace(N, size):
     return n
 
 
-def augment_batch(img_u8, mask_u8, params, size, out=None, workspace=None, host_params=None):
+def augment_batch(img_u8, mask_u8, params, size, out=None, workspace=None, host_params=None, field=None):
     """uint8 (N,H,W,C) images + uint8 (N,H,W) masks -> (float32 (N,C,th,tw) in [0,1], int64 (N,th,tw)): crop, flip, colour
     jitter and affine map of each image by its record of the float32 (N,P) device table `params` (medt_amd.augment.draw_record).
     size = (th, tw).  out: an (image, mask) pair to write into (contiguous; a view that is not 16-byte aligned takes the
     kernels' element stores).  workspace: augment_workspace() floats; after the call its last N floats hold the means the
     contrast operations used.  host_params: the table as a CPU tensor, when the caller has it (the prefetcher does): the origin
-    check and the choice of launches read it instead of copying `params` back, which waits for the device."""
+    check and the choice of launches read it instead of copying `params` back, which waits for the device.
+    field: the float32 (N,2,G+3,G+3) control lattices of the elastic deformation on the images' device, 1 <= G <= 8
+    (medt_amd.augment.draw_field); the records whose slot 18 is set are deformed by theirs (medt_augment_warp), and a batch
+    in which none is set takes the launches it takes without a field."""
     if img_u8.dtype != torch.uint8 or mask_u8.dtype != torch.uint8:
         raise L.MedtError("augment_batch: uint8 images and masks expected")
     _require_device(params)                # (a float32 device tensor; images and masks must live where the table does, below)
@@ -946,6 +951,16 @@ def augment_batch(img_u8, mask_u8, params, size, out=None, workspace=None, host_
     if not (bool((cy >= 0).all()) and bool((cx >= 0).all()) and bool((cy + th <= H).all()) and bool((cx + tw <= W).all())):
         raise L.MedtError(f"augment_batch: a crop origin puts the {th} x {tw} window outside the {H} x {W} image")
     use_stats = bool((host[:, 10:14] == AUG_CONTRAST).any())
+    G = 0
+    if field is not None:
+        _require_device(field)
+        G = int(field.shape[-1]) - 3 if field.dim() == 4 else 0
+        if (field.dtype != torch.float32 or field.dim() != 4 or tuple(field.shape) != (N, 2, G + 3, G + 3)
+                or not 1 <= G <= AUG_ELASTIC_MAX_GRID or not field.is_contiguous() or field.device != img_u8.device):
+            raise L.MedtError(f"augment_batch: field must be a contiguous float32 ({N},2,G+3,G+3) lattice on the images' device, "
+                              f"1 <= G <= {AUG_ELASTIC_MAX_GRID}")
+        if not bool((host[:, AUG_ELASTIC_SLOT] != 0).any()):
+            field = None                   # no record asks for it: the launches of a call without a field
     img_u8, mask_u8 = img_u8.contiguous(), mask_u8.contiguous()
     if out is None:
         out = (torch.empty((N, Cc, th, tw), device=img_u8.device, dtype=torch.float32),
@@ -963,6 +978,11 @@ def augment_batch(img_u8, mask_u8, params, size, out=None, workspace=None, host_
     if use_stats:
         L.check(lib.medt_augment_stats(img_u8.data_ptr(), params.data_ptr(), workspace.data_ptr(), N, H, W, Cc, th, tw, _stream()),
                 "medt_augment_stats")
+    if field is not None:
+        L.check(lib.medt_augment_warp(img_u8.data_ptr(), mask_u8.data_ptr(), params.data_ptr(), field.data_ptr(), G, L.ptr(workspace),
+                                      oi.data_ptr(), om.data_ptr(), N, H, W, Cc, th, tw, int(use_stats), _stream()),
+                "medt_augment_warp")
+        return oi, om
     L.check(lib.medt_augment_apply(img_u8.data_ptr(), mask_u8.data_ptr(), params.data_ptr(), L.ptr(workspace), oi.data_ptr(),
                                    om.data_ptr(), N, H, W, Cc, th, tw, int(use_stats), _stream()), "medt_augment_apply")
     return oi, om

@@ -23,6 +23,9 @@ Differences, all host-side plumbing:
   * --aug on moves the joint transform to the GPU (medt_amd.augment: the uint8 image is uploaded, two kernels crop, flip,
     jitter and map it); --aug_jitter "b,c,s,h" and --aug_affine P add the colour jitter and the random affine map the
     reference's JointTransform2D has and its train.py never enables; --aug off (the default) is the host transform as before;
+  * --aug_elastic P adds U-Net's elastic deformation to --aug on: with probability P an item gets a cubic B-spline deformation
+    over --aug_elastic_grid x --aug_elastic_grid cells of random displacements with standard deviation --aug_elastic_sigma
+    pixels, the image sampled bilinearly, the mask nearest (printed once as `elastic p .. grid .. sigma ..`);
   * the per-step threshold-and-copy-to-host of the output (train.py:142-152) is dropped: its result is unused.
 """
 import argparse
@@ -56,6 +59,9 @@ parser.add_argument('--cuda', default="on", type=str, help='switch on/off cuda o
 parser.add_argument('--aug', default='off', type=str, help='turn on img augmentation (default: False)')
 parser.add_argument('--aug_jitter', default=None, type=str, help='with --aug on: colour jitter ranges "brightness,contrast,saturation,hue", e.g. "0.2,0.2,0.2,0.05"')
 parser.add_argument('--aug_affine', default=None, type=float, help='with --aug on: probability of the random affine map (rotation, shear, scale 2, translation)')
+parser.add_argument('--aug_elastic', default=None, type=float, help='with --aug on: probability of the elastic deformation (cubic B-spline over a coarse grid of random displacements)')
+parser.add_argument('--aug_elastic_grid', default=None, type=int, help='with --aug_elastic: cells per side of the coarse grid, 1 .. 8 (default: 3)')
+parser.add_argument('--aug_elastic_sigma', default=None, type=float, help='with --aug_elastic: standard deviation of the displacements in pixels (default: 4.0)')
 parser.add_argument('--load', default='default', type=str, help='load a pretrained model')
 parser.add_argument('--save', default='default', type=str, help='save the model')
 parser.add_argument('--direc', default='./medt', type=str, help='directory to save')
@@ -138,14 +144,16 @@ def make_criterion(loss, class_weights, boundary=None, border=None):
     return DiceCELoss(weight=weight, ce=0.0 if loss == "dice" else 1.0, dice=1.0)
 
 
-def make_augment(aug, aug_jitter, aug_affine):
+def make_augment(aug, aug_jitter, aug_affine, aug_elastic=None, aug_elastic_grid=None, aug_elastic_sigma=None):
     """None for --aug off (the host transform, as before), else the settings of the device-side transform: the defaults are
-    the host transform's (crop from --crop, flip 0.5, no jitter, no affine map)."""
+    the host transform's (crop from --crop, flip 0.5, no jitter, no affine map).  An "elastic" entry only with --aug_elastic > 0."""
     if aug != "on":                 # (any other value was parsed and ignored before the device path existed: still the host path)
         if aug_jitter is not None or aug_affine is not None:
             raise SystemExit("--aug_jitter / --aug_affine belong to the device-side augmentation: add --aug on")
+        if aug_elastic is not None or aug_elastic_grid is not None or aug_elastic_sigma is not None:
+            raise SystemExit("--aug_elastic / --aug_elastic_grid / --aug_elastic_sigma belong to the device-side augmentation: add --aug on")
         return None
-    from medt_amd.augment import parse_jitter
+    from medt_amd.augment import ELASTIC_MAX_GRID, parse_jitter
     jitter = None
     if aug_jitter is not None:
         try:
@@ -155,7 +163,22 @@ def make_augment(aug, aug_jitter, aug_affine):
     p_affine = 0.0 if aug_affine is None else aug_affine
     if not 0.0 <= p_affine <= 1.0:
         raise SystemExit("--aug_affine: a probability in [0, 1] expected, got %r" % aug_affine)
-    return {"jitter": jitter, "p_affine": p_affine}
+    augment = {"jitter": jitter, "p_affine": p_affine}
+    if aug_elastic is None:
+        if aug_elastic_grid is not None or aug_elastic_sigma is not None:
+            raise SystemExit("--aug_elastic_grid / --aug_elastic_sigma belong to the elastic deformation: add --aug_elastic P")
+        return augment
+    grid = 3 if aug_elastic_grid is None else aug_elastic_grid
+    sigma = 4.0 if aug_elastic_sigma is None else aug_elastic_sigma
+    if not 0.0 <= aug_elastic <= 1.0:
+        raise SystemExit("--aug_elastic: a probability in [0, 1] expected, got %r" % aug_elastic)
+    if not 1 <= grid <= ELASTIC_MAX_GRID:
+        raise SystemExit("--aug_elastic_grid: 1 .. %d cells per side expected, got %r" % (ELASTIC_MAX_GRID, grid))
+    if not 0.0 <= sigma < float("inf"):
+        raise SystemExit("--aug_elastic_sigma: a finite standard deviation >= 0 in pixels expected, got %r" % sigma)
+    if aug_elastic > 0.0:
+        augment["elastic"] = {"p": aug_elastic, "grid": grid, "sigma": sigma}
+    return augment
 
 
 def main():
@@ -163,7 +186,8 @@ def main():
     boundary = make_boundary(args.loss, args.boundary_alpha, args.boundary_step, args.boundary_max)    # (so do --boundary_* alone)
     border = make_border(args.loss, args.border_w0, args.border_sigma, args.border_connectivity)        # (and --border_* alone)
     criterion = make_criterion(args.loss, args.class_weights, boundary, border)      # (a bad --class_weights ends the run before any work)
-    augment = make_augment(args.aug, args.aug_jitter, args.aug_affine)              # (so does a bad --aug_* combination)
+    augment = make_augment(args.aug, args.aug_jitter, args.aug_affine, args.aug_elastic, args.aug_elastic_grid,
+                           args.aug_elastic_sigma)                                   # (so does a bad --aug_* combination)
     direc, modelname, imgsize = args.direc, args.modelname, args.imgsize
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -196,10 +220,12 @@ def main():
     crop = (args.crop, args.crop) if args.crop is not None else None
     tf_train = JointTransform2D(crop=crop, p_flip=0.5, color_jitter_params=None, long_mask=True)
     tf_val = JointTransform2D(crop=crop, p_flip=0, color_jitter_params=None, long_mask=True)
-    device_aug = None
+    device_aug = elastic = None
     if augment is not None:        # the draws stay per item on the host; crop / flip / jitter / affine run on the device
         from medt_amd.augment import DeviceAugment, RawJointTransform2D
-        tf_train = RawJointTransform2D(crop=crop, p_flip=0.5, jitter=augment["jitter"], p_affine=augment["p_affine"])
+        elastic = augment.get("elastic")
+        tf_train = RawJointTransform2D(crop=crop, p_flip=0.5, jitter=augment["jitter"], p_affine=augment["p_affine"],
+                                       **({"elastic": elastic} if elastic else {}))
         device_aug = DeviceAugment(crop)
     train_dataset = ImageToImage2D(args.train_dataset, tf_train)
     val_dataset = ImageToImage2D(args.val_dataset or args.train_dataset, tf_val)
@@ -224,6 +250,8 @@ def main():
     infer_step = InferStep(model, use_graph=not args.eager)
     if rank == 0:
         print("Total_params: {}".format(sum(p.numel() for p in model.parameters() if p.requires_grad)))
+    if rank == 0 and elastic is not None:
+        print('elastic p {:.4f} grid {} sigma {:.4f}'.format(elastic["p"], elastic["grid"], elastic["sigma"]))
     if rank == 0 and border is not None:
         print('border w0 {:.4f} sigma {:.4f} connectivity {}'.format(border["w0"], border["sigma"], border["connectivity"]))
 
@@ -239,11 +267,15 @@ def main():
         if boundary is not None:                  # filled in place: the captured step reads the weight from device memory
             criterion.set_alpha(boundary_alpha(boundary, epoch))
         # host decode + pinned staging + H2D run one step ahead on a copy stream (reference: blocking .to(), :134-135)
-        for batch_idx, (X_batch, y_batch, *rest) in enumerate(DevicePrefetcher(dataloader, device, stage=3 if device_aug else 2)):
+        stage = (4 if elastic else 3) if device_aug else 2          # + the record table, + the elastic control lattices
+        for batch_idx, (X_batch, y_batch, *rest) in enumerate(DevicePrefetcher(dataloader, device, stage=stage)):
             X_batch = X_batch.to(device)
             y_batch = y_batch.to(device)
             if device_aug is not None:            # uint8 HWC batch + its record table -> float32 NCHW images, int64 masks
-                X_batch, y_batch = device_aug(X_batch, y_batch, rest[0].to(device))
+                if elastic:
+                    X_batch, y_batch = device_aug(X_batch, y_batch, rest[0].to(device), field=rest[1].to(device))
+                else:
+                    X_batch, y_batch = device_aug(X_batch, y_batch, rest[0].to(device))
             loss = train_step(X_batch, y_batch)
             epoch_running_loss += loss.item()
             train_step.check_targets()            # mislabelled masks raise, as F.cross_entropy does in the reference
