@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import Callable, NamedTuple
 
 import torch
 
@@ -387,6 +388,15 @@ def logo_merge(x, yp, P=32, G=4):
 # --------------------------------------------------------------------------- #
 # cross entropy
 # --------------------------------------------------------------------------- #
+def _nkhw(logits):
+    return logits.shape[0], logits.shape[1], logits[0, 0].numel()
+
+
+def _grad_buffers(logits, dloss):
+    """What every loss backward starts from -> (N, K, HW), the incoming gradient as float32, an empty dlogits."""
+    return _nkhw(logits), dloss.contiguous().float(), torch.empty_like(logits)
+
+
 class CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, ignore_index):
@@ -395,8 +405,7 @@ class CrossEntropyFn(torch.autograd.Function):
         logits, target = logits.contiguous(), target.contiguous()
         if target.dtype != torch.int64:
             raise L.MedtError("cross_entropy: int64 class-index targets expected")
-        N, K = logits.shape[0], logits.shape[1]
-        HW = logits[0, 0].numel()
+        N, K, HW = _nkhw(logits)
         partials = torch.empty((lib.medt_ce_partials(N, HW),), device=logits.device, dtype=torch.float32)
         out = torch.empty((3,), device=logits.device, dtype=torch.float32)
         L.check(lib.medt_ce_fwd(logits.data_ptr(), target.data_ptr(), partials.data_ptr(), out.data_ptr(), N, K, HW,
@@ -414,10 +423,7 @@ class CrossEntropyFn(torch.autograd.Function):
             return None, None, None
         lib = L.lib()
         logits, target, out = ctx.saved_tensors
-        N, K = logits.shape[0], logits.shape[1]
-        HW = logits[0, 0].numel()
-        dloss = dloss.contiguous().float()
-        dlogits = torch.empty_like(logits)
+        (N, K, HW), dloss, dlogits = _grad_buffers(logits, dloss)
         L.check(lib.medt_ce_bwd(logits.data_ptr(), target.data_ptr(), out.data_ptr(), dloss.data_ptr(),
                                 dlogits.data_ptr(), N, K, HW, ctx.ignore_index, _stream()), "medt_ce_bwd")
         return dlogits, None, None
@@ -433,10 +439,7 @@ def cross_entropy(logits, target, ignore_index=-100):
     wrapper raises MedtError from the count (one host sync; skipped while a hipGraph is being captured -- TrainStep
     checks the same counter after the replay -- and when MEDT_CHECK_TARGETS=0)."""
     loss, out = CrossEntropyFn.apply(logits, target, ignore_index)
-    loss._medt_ce_out = out                       # [mean loss, counted pixels, out-of-range targets]
-    if CHECK_TARGETS and not torch.cuda.is_current_stream_capturing():
-        raise_on_bad_targets(out, logits.shape[1])
-    return loss
+    return _with_ce_out(loss, out, logits.shape[1])           # [mean loss, counted pixels, out-of-range targets]
 
 
 def raise_on_bad_targets(out, K):
@@ -447,24 +450,43 @@ def raise_on_bad_targets(out, K):
                           "(torch.nn.functional.cross_entropy raises on these too)")
 
 
+def _with_ce_out(loss, out, K):
+    """Attach the `out` whose slot 2 counts the out-of-range targets, and raise on them where a host sync is allowed."""
+    loss._medt_ce_out = out
+    if CHECK_TARGETS and not torch.cuda.is_current_stream_capturing():
+        raise_on_bad_targets(out, K)
+    return loss
+
+
 # --------------------------------------------------------------------------- #
 # class-weighted cross entropy + soft Dice
 # --------------------------------------------------------------------------- #
+def _region_fwd(what, logits, target, weight, N, K, HW, ce, dice, eps, ignore_index):
+    """The region term's forward on contiguous logits / targets -> its `out`.  `what`: the public function, for the message."""
+    lib = L.lib()
+    nws, nout = lib.medt_seg_loss_workspace(N, K, HW), lib.medt_seg_loss_out_floats(N, K)
+    if not nws or not nout:
+        raise L.MedtError(f"{what}: {lib.medt_last_error().decode()}")
+    partials = torch.empty((nws,), device=logits.device, dtype=torch.float32)
+    out = torch.empty((nout,), device=logits.device, dtype=torch.float32)
+    L.check(lib.medt_seg_loss_fwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), partials.data_ptr(), out.data_ptr(),
+                                  N, K, HW, ignore_index, ce, dice, eps, _stream()), "medt_seg_loss_fwd")
+    return out
+
+
+def _region_bwd(logits, target, weight, out, dloss, dlogits, N, K, HW, ce, dice, eps, ignore_index):
+    """The region term's backward: writes (does not add into) every element of `dlogits`."""
+    L.check(L.lib().medt_seg_loss_bwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), out.data_ptr(), dloss.data_ptr(),
+                                      dlogits.data_ptr(), N, K, HW, ignore_index, ce, dice, eps, _stream()),
+            "medt_seg_loss_bwd")
+
+
 class SegLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, weight, ce, dice, eps, ignore_index):
         _require_device(logits)
-        lib = L.lib()
         logits, target = logits.contiguous(), target.contiguous()
-        N, K = logits.shape[0], logits.shape[1]
-        HW = logits[0, 0].numel()
-        nws, nout = lib.medt_seg_loss_workspace(N, K, HW), lib.medt_seg_loss_out_floats(N, K)
-        if not nws or not nout:
-            raise L.MedtError(f"seg_loss: {lib.medt_last_error().decode()}")
-        partials = torch.empty((nws,), device=logits.device, dtype=torch.float32)
-        out = torch.empty((nout,), device=logits.device, dtype=torch.float32)
-        L.check(lib.medt_seg_loss_fwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), partials.data_ptr(), out.data_ptr(),
-                                      N, K, HW, ignore_index, ce, dice, eps, _stream()), "medt_seg_loss_fwd")
+        out = _region_fwd("seg_loss", logits, target, weight, *_nkhw(logits), ce, dice, eps, ignore_index)
         ctx.save_for_backward(logits, target, out, weight)
         ctx.cfg = (ce, dice, eps, ignore_index)
         loss = out[0]
@@ -476,17 +498,29 @@ class SegLossFn(torch.autograd.Function):
     def backward(ctx, dloss, _dout):
         if dloss is None:
             return (None,) * 7
-        lib = L.lib()
         logits, target, out, weight = ctx.saved_tensors
-        ce, dice, eps, ignore_index = ctx.cfg
-        N, K = logits.shape[0], logits.shape[1]
-        HW = logits[0, 0].numel()
-        dloss = dloss.contiguous().float()
-        dlogits = torch.empty_like(logits)
-        L.check(lib.medt_seg_loss_bwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), out.data_ptr(), dloss.data_ptr(),
-                                      dlogits.data_ptr(), N, K, HW, ignore_index, ce, dice, eps, _stream()),
-                "medt_seg_loss_bwd")
+        dims, dloss, dlogits = _grad_buffers(logits, dloss)
+        _region_bwd(logits, target, weight, out, dloss, dlogits, *dims, *ctx.cfg)
         return (dlogits,) + (None,) * 6
+
+
+def _region_args(what, logits, weight, ce, dice, eps, required=False):
+    """The checks of the region term's options -> (weight, ce, dice, eps) as the nodes take them.  required: `what` is a
+    seg_<term>_loss, which refuses ce == dice == 0 and names <term>_loss() for that."""
+    K = logits.shape[1]
+    if weight is not None:
+        if (not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.dim() != 1 or weight.numel() != K
+                or weight.device != logits.device):
+            raise L.MedtError(f"{what}: weight must be a float32 tensor of {K} class weights on the logits' device")
+        weight = weight.detach().contiguous()
+    ce, dice, eps = float(ce), float(dice), float(eps)
+    if required and ce == 0.0 and dice == 0.0:
+        raise L.MedtError(f"{what}: no region term (ce == dice == 0): {what[len('seg_'):]}() is the term alone")
+    if dice != 0.0 and not 2 <= K <= 8:
+        raise L.MedtError(f"{what}: soft Dice needs 2 <= K <= 8 classes (K = {K})")
+    if not eps >= 0.0:
+        raise L.MedtError(f"{what}: eps >= 0 expected")
+    return weight, ce, dice, eps
 
 
 def seg_loss(logits, target, weight=None, ce=1.0, dice=0.0, eps=1.0, ignore_index=-100):
@@ -511,62 +545,75 @@ def seg_loss(logits, target, weight=None, ce=1.0, dice=0.0, eps=1.0, ignore_inde
         raise L.MedtError("seg_loss: float32 (N,K,...) logits expected")
     if target.dtype != torch.int64 or target.device != logits.device or target.numel() * logits.shape[1] != logits.numel():
         raise L.MedtError("seg_loss: int64 (N,...) class-index targets on the logits' device expected")
-    K = logits.shape[1]
-    if weight is not None:
-        if (not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.dim() != 1 or weight.numel() != K
-                or weight.device != logits.device):
-            raise L.MedtError(f"seg_loss: weight must be a float32 tensor of {K} class weights on the logits' device")
-        weight = weight.detach().contiguous()
-    ce, dice, eps = float(ce), float(dice), float(eps)
-    if dice != 0.0 and not 2 <= K <= 8:
-        raise L.MedtError(f"seg_loss: soft Dice needs 2 <= K <= 8 classes (K = {K})")
-    if not eps >= 0.0:
-        raise L.MedtError("seg_loss: eps >= 0 expected")
+    weight, ce, dice, eps = _region_args("seg_loss", logits, weight, ce, dice, eps)
     loss, out = SegLossFn.apply(logits, target, weight, ce, dice, eps, int(ignore_index))
-    loss._medt_ce_out = out                       # [loss, sum of counted weights, out-of-range targets, CE, Dice, ...]
-    if CHECK_TARGETS and not torch.cuda.is_current_stream_capturing():
-        raise_on_bad_targets(out, K)
-    return loss
+    return _with_ce_out(loss, out, logits.shape[1])       # [loss, sum of counted weights, out-of-range targets, CE, Dice, ...]
 
 
 # --------------------------------------------------------------------------- #
-# boundary loss (Kervadec et al., MIDL 2019) on the signed distance map of the step's own label map
+# region loss + one weighted extra term on maps derived from the step's own label map: the boundary loss (Kervadec et al.,
+# MIDL 2019) on its signed distance map, or the border weight for touching objects (Ronneberger et al., U-Net, 2015) on the
+# distances to its two nearest components
 # --------------------------------------------------------------------------- #
-class SegBoundaryFn(torch.autograd.Function):
-    """region loss (medt_seg_loss_*, unchanged; left out when ce == dice == 0) + alpha * boundary term as ONE node: the
-    boundary finalize adds the region loss on the device, the boundary backward adds into the region backward's dlogits."""
+def _boundary_maps(target, fg, ignore_index, connectivity):
+    return (signed_edt_sq(target, fg, ignore_index),)
+
+
+def _border_maps(target, fg, ignore_index, connectivity):
+    """{target == fg} as a uint8 mask (torch), label() -> object_edt2_sq(); nothing syncs."""
+    mask = torch.empty(target.shape, device=target.device, dtype=torch.uint8)
+    torch.eq(target, fg, out=mask)                             # F as the uint8 mask label() takes, in one launch
+    if fg == ignore_index:                                     # an ignored pixel is not in F
+        mask.zero_()
+    labels, _ = label(mask, connectivity)
+    return object_edt2_sq(labels)
+
+
+class _Term(NamedTuple):
+    """An extra term of the loss: its name in messages, the attribute of the loss that holds its `out`, the int32 maps it derives
+    from (target, fg, ignore_index, connectivity), its C entry points.  Forward and backward take (logits, target, *maps,
+    [sigma,] ...): sigma is None for a term without one."""
+    what: str
+    side: str
+    maps: Callable
+    workspace: str
+    out_floats: str
+    fwd: str
+    bwd: str
+
+
+BOUNDARY = _Term("boundary_loss", "_medt_boundary_out", _boundary_maps, "medt_boundary_workspace", "medt_boundary_out_floats",
+                 "medt_boundary_fwd", "medt_boundary_bwd")
+BORDER = _Term("border_loss", "_medt_border_out", _border_maps, "medt_border_workspace", "medt_border_out_floats",
+               "medt_border_fwd", "medt_border_bwd")
+
+
+class SegTermFn(torch.autograd.Function):
+    """region loss (medt_seg_loss_*, unchanged; left out when ce == dice == 0) + scale * one extra term as ONE node: the term's
+    finalize adds the region loss on the device, the term's backward adds into the region backward's dlogits."""
 
     @staticmethod
-    def forward(ctx, logits, target, alpha, weight, ce, dice, eps, fg, ignore_index):
+    def forward(ctx, logits, target, scale, weight, ce, dice, eps, fg, ignore_index, term, connectivity, sigma):
         _require_device(logits)
         lib = L.lib()
         logits, target = logits.contiguous(), target.contiguous()
-        N, K = logits.shape[0], logits.shape[1]
-        HW = logits[0, 0].numel()
+        N, K, HW = _nkhw(logits)
         region = ce != 0.0 or dice != 0.0
-        rout = None
-        if region:
-            nws, nout = lib.medt_seg_loss_workspace(N, K, HW), lib.medt_seg_loss_out_floats(N, K)
-            if not nws or not nout:
-                raise L.MedtError(f"seg_boundary_loss: {lib.medt_last_error().decode()}")
-            partials = torch.empty((nws,), device=logits.device, dtype=torch.float32)
-            rout = torch.empty((nout,), device=logits.device, dtype=torch.float32)
-            L.check(lib.medt_seg_loss_fwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), partials.data_ptr(), rout.data_ptr(),
-                                          N, K, HW, ignore_index, ce, dice, eps, _stream()), "medt_seg_loss_fwd")
-        sd2 = signed_edt_sq(target, fg, ignore_index)
-        nws, nout = lib.medt_boundary_workspace(N, HW), lib.medt_boundary_out_floats(N)
+        rout = _region_fwd("seg_" + term.what, logits, target, weight, N, K, HW, ce, dice, eps, ignore_index) if region else None
+        maps = term.maps(target, fg, ignore_index, connectivity)
+        nws, nout = getattr(lib, term.workspace)(N, HW), getattr(lib, term.out_floats)(N)
         if not nws or not nout:
-            raise L.MedtError(f"boundary_loss: {lib.medt_last_error().decode()}")
-        bparts = torch.empty((nws,), device=logits.device, dtype=torch.float32)
-        bout = torch.empty((nout,), device=logits.device, dtype=torch.float32)
-        L.check(lib.medt_boundary_fwd(logits.data_ptr(), target.data_ptr(), sd2.data_ptr(), alpha.data_ptr(), L.ptr(rout),
-                                      bparts.data_ptr(), bout.data_ptr(), N, K, HW, fg, ignore_index, _stream()),
-                "medt_boundary_fwd")
-        saved = [logits, target, sd2, bout] + ([rout] if region else []) + ([weight] if weight is not None else [])
-        ctx.save_for_backward(*saved)
-        ctx.cfg = (ce, dice, eps, fg, ignore_index, region, weight is not None)
-        loss = bout[0]
-        outs = (bout, rout) if region else (bout,)
+            raise L.MedtError(f"{term.what}: {lib.medt_last_error().decode()}")
+        parts = torch.empty((nws,), device=logits.device, dtype=torch.float32)
+        tout = torch.empty((nout,), device=logits.device, dtype=torch.float32)
+        head = [logits.data_ptr(), target.data_ptr()] + [m.data_ptr() for m in maps] + ([] if sigma is None else [sigma])
+        L.check(getattr(lib, term.fwd)(*head, scale.data_ptr(), L.ptr(rout), parts.data_ptr(), tout.data_ptr(), N, K, HW, fg,
+                                       ignore_index, _stream()), term.fwd)
+        ctx.save_for_backward(logits, target, tout, rout, weight, *maps)           # (rout, weight: None where there is none)
+        ctx.cfg = (ce, dice, eps, ignore_index)
+        ctx.term = (term, fg, sigma)
+        loss = tout[0]
+        outs = (tout, rout) if region else (tout,)
         ctx.mark_non_differentiable(*outs)
         ctx.set_materialize_grads(False)
         return (loss,) + outs
@@ -574,24 +621,28 @@ class SegBoundaryFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, *_):
         if dloss is None:
-            return (None,) * 9
-        lib = L.lib()
-        ce, dice, eps, fg, ignore_index, region, weighted = ctx.cfg
-        logits, target, sd2, bout, *rest = ctx.saved_tensors
-        rout = rest.pop(0) if region else None
-        weight = rest.pop(0) if weighted else None
-        N, K = logits.shape[0], logits.shape[1]
-        HW = logits[0, 0].numel()
-        dloss = dloss.contiguous().float()
-        dlogits = torch.empty_like(logits)
+            return (None,) * 12
+        term, fg, sigma = ctx.term
+        logits, target, tout, rout, weight, *maps = ctx.saved_tensors
+        (N, K, HW), dloss, dlogits = _grad_buffers(logits, dloss)
+        region = rout is not None
         if region:
-            L.check(lib.medt_seg_loss_bwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), rout.data_ptr(), dloss.data_ptr(),
-                                          dlogits.data_ptr(), N, K, HW, ignore_index, ce, dice, eps, _stream()),
-                    "medt_seg_loss_bwd")
-        L.check(lib.medt_boundary_bwd(logits.data_ptr(), target.data_ptr(), sd2.data_ptr(), bout.data_ptr(), dloss.data_ptr(),
-                                      dlogits.data_ptr(), N, K, HW, fg, ignore_index, int(region), _stream()),
-                "medt_boundary_bwd")
-        return (dlogits,) + (None,) * 8
+            _region_bwd(logits, target, weight, rout, dloss, dlogits, N, K, HW, *ctx.cfg)
+        head = [logits.data_ptr(), target.data_ptr()] + [m.data_ptr() for m in maps] + ([] if sigma is None else [sigma])
+        L.check(getattr(L.lib(), term.bwd)(*head, tout.data_ptr(), dloss.data_ptr(), dlogits.data_ptr(), N, K, HW, fg, ctx.cfg[3],
+                                           int(region), _stream()), term.bwd)
+        return (dlogits,) + (None,) * 11
+
+
+def _seg_term(term, logits, target, scale, region, fg, ignore_index, connectivity=None, sigma=None):
+    """One SegTermFn node -> loss with its side outputs.  region: (weight, ce, dice, eps) as given to a seg_<term>_loss, None for
+    the term alone."""
+    K = logits.shape[1]
+    weight, ce, dice, eps = (None, 0.0, 0.0, 1.0) if region is None else _region_args("seg_" + term.what, logits, *region, required=True)
+    loss, tout, *rout = SegTermFn.apply(logits, target, scale, weight, ce, dice, eps, int(fg), int(ignore_index), term, connectivity,
+                                        sigma)
+    setattr(loss, term.side, tout)
+    return _with_ce_out(loss, rout[0], K) if rout else loss
 
 
 def _boundary_args(what, logits, target, alpha, fg):
@@ -620,9 +671,7 @@ def boundary_loss(logits, target, alpha, fg=1, ignore_index=-100):
     READ ON THE DEVICE by the kernels (refill it in place and a captured step follows), or a number.  Two launches for the map,
     two forward, one backward; no float atomics.  loss._medt_boundary_out = [alpha B, B, alpha, ...]."""
     alpha = _boundary_args("boundary_loss", logits, target, alpha, fg)
-    loss, bout = SegBoundaryFn.apply(logits, target, alpha, None, 0.0, 0.0, 1.0, int(fg), int(ignore_index))
-    loss._medt_boundary_out = bout
-    return loss
+    return _seg_term(BOUNDARY, logits, target, alpha, None, fg, ignore_index)
 
 
 def seg_boundary_loss(logits, target, alpha, weight=None, ce=1.0, dice=0.0, eps=1.0, fg=1, ignore_index=-100):
@@ -632,96 +681,7 @@ def seg_boundary_loss(logits, target, alpha, weight=None, ce=1.0, dice=0.0, eps=
     add.  With alpha == 0 loss and gradient are seg_loss's, bit for bit.  loss._medt_ce_out is the region term's `out` (so
     TrainStep.check_targets() works as with seg_loss), loss._medt_boundary_out = [loss, B, alpha, ...]."""
     alpha = _boundary_args("seg_boundary_loss", logits, target, alpha, fg)
-    K = logits.shape[1]
-    if weight is not None:
-        if (not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.dim() != 1 or weight.numel() != K
-                or weight.device != logits.device):
-            raise L.MedtError(f"seg_boundary_loss: weight must be a float32 tensor of {K} class weights on the logits' device")
-        weight = weight.detach().contiguous()
-    ce, dice, eps = float(ce), float(dice), float(eps)
-    if ce == 0.0 and dice == 0.0:
-        raise L.MedtError("seg_boundary_loss: no region term (ce == dice == 0): boundary_loss() is the term alone")
-    if dice != 0.0 and not 2 <= K <= 8:
-        raise L.MedtError(f"seg_boundary_loss: soft Dice needs 2 <= K <= 8 classes (K = {K})")
-    if not eps >= 0.0:
-        raise L.MedtError("seg_boundary_loss: eps >= 0 expected")
-    loss, bout, rout = SegBoundaryFn.apply(logits, target, alpha, weight, ce, dice, eps, int(fg), int(ignore_index))
-    loss._medt_ce_out = rout
-    loss._medt_boundary_out = bout
-    if CHECK_TARGETS and not torch.cuda.is_current_stream_capturing():
-        raise_on_bad_targets(rout, K)
-    return loss
-
-
-# --------------------------------------------------------------------------- #
-# border weight for touching objects (Ronneberger et al., U-Net, 2015) on the components of the step's own label map
-# --------------------------------------------------------------------------- #
-class SegBorderFn(torch.autograd.Function):
-    """region loss (medt_seg_loss_*, unchanged; left out when ce == dice == 0) + w0 * border term as ONE node, as SegBoundaryFn:
-    the finalize adds the region loss on the device, the border backward adds into the region backward's dlogits.  The maps come
-    from the targets inside the node: {target == fg} as a uint8 mask (torch), label() -> object_edt2_sq(); nothing syncs."""
-
-    @staticmethod
-    def forward(ctx, logits, target, w0, weight, ce, dice, eps, fg, connectivity, ignore_index, sigma):
-        _require_device(logits)
-        lib = L.lib()
-        logits, target = logits.contiguous(), target.contiguous()
-        N, K = logits.shape[0], logits.shape[1]
-        HW = logits[0, 0].numel()
-        region = ce != 0.0 or dice != 0.0
-        rout = None
-        if region:
-            nws, nout = lib.medt_seg_loss_workspace(N, K, HW), lib.medt_seg_loss_out_floats(N, K)
-            if not nws or not nout:
-                raise L.MedtError(f"seg_border_loss: {lib.medt_last_error().decode()}")
-            partials = torch.empty((nws,), device=logits.device, dtype=torch.float32)
-            rout = torch.empty((nout,), device=logits.device, dtype=torch.float32)
-            L.check(lib.medt_seg_loss_fwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), partials.data_ptr(), rout.data_ptr(),
-                                          N, K, HW, ignore_index, ce, dice, eps, _stream()), "medt_seg_loss_fwd")
-        mask = torch.empty(target.shape, device=target.device, dtype=torch.uint8)
-        torch.eq(target, fg, out=mask)                             # F as the uint8 mask label() takes, in one launch
-        if fg == ignore_index:                                     # an ignored pixel is not in F
-            mask.zero_()
-        labels, _ = label(mask, connectivity)
-        d1, d2 = object_edt2_sq(labels)
-        nws, nout = lib.medt_border_workspace(N, HW), lib.medt_border_out_floats(N)
-        if not nws or not nout:
-            raise L.MedtError(f"border_loss: {lib.medt_last_error().decode()}")
-        bparts = torch.empty((nws,), device=logits.device, dtype=torch.float32)
-        bout = torch.empty((nout,), device=logits.device, dtype=torch.float32)
-        L.check(lib.medt_border_fwd(logits.data_ptr(), target.data_ptr(), d1.data_ptr(), d2.data_ptr(), sigma, w0.data_ptr(),
-                                    L.ptr(rout), bparts.data_ptr(), bout.data_ptr(), N, K, HW, fg, ignore_index, _stream()),
-                "medt_border_fwd")
-        saved = [logits, target, d1, d2, bout] + ([rout] if region else []) + ([weight] if weight is not None else [])
-        ctx.save_for_backward(*saved)
-        ctx.cfg = (ce, dice, eps, fg, ignore_index, sigma, region, weight is not None)
-        loss = bout[0]
-        outs = (bout, rout) if region else (bout,)
-        ctx.mark_non_differentiable(*outs)
-        ctx.set_materialize_grads(False)
-        return (loss,) + outs
-
-    @staticmethod
-    def backward(ctx, dloss, *_):
-        if dloss is None:
-            return (None,) * 11
-        lib = L.lib()
-        ce, dice, eps, fg, ignore_index, sigma, region, weighted = ctx.cfg
-        logits, target, d1, d2, bout, *rest = ctx.saved_tensors
-        rout = rest.pop(0) if region else None
-        weight = rest.pop(0) if weighted else None
-        N, K = logits.shape[0], logits.shape[1]
-        HW = logits[0, 0].numel()
-        dloss = dloss.contiguous().float()
-        dlogits = torch.empty_like(logits)
-        if region:
-            L.check(lib.medt_seg_loss_bwd(logits.data_ptr(), target.data_ptr(), L.ptr(weight), rout.data_ptr(), dloss.data_ptr(),
-                                          dlogits.data_ptr(), N, K, HW, ignore_index, ce, dice, eps, _stream()),
-                    "medt_seg_loss_bwd")
-        L.check(lib.medt_border_bwd(logits.data_ptr(), target.data_ptr(), d1.data_ptr(), d2.data_ptr(), sigma, bout.data_ptr(),
-                                    dloss.data_ptr(), dlogits.data_ptr(), N, K, HW, fg, ignore_index, int(region), _stream()),
-                "medt_border_bwd")
-        return (dlogits,) + (None,) * 10
+    return _seg_term(BOUNDARY, logits, target, alpha, (weight, ce, dice, eps), fg, ignore_index)
 
 
 def _border_args(what, logits, target, w0, sigma, fg, connectivity):
@@ -745,9 +705,7 @@ def border_loss(logits, target, w0, sigma=5.0, fg=1, connectivity=8, ignore_inde
     float32 device tensor, READ ON THE DEVICE by the kernels (refill it in place and a captured step follows), or a number.
     No host sync, no float atomics.  loss._medt_border_out = [w0 R, R, w0, ...]."""
     w0, sigma = _border_args("border_loss", logits, target, w0, sigma, fg, connectivity)
-    loss, bout = SegBorderFn.apply(logits, target, w0, None, 0.0, 0.0, 1.0, int(fg), int(connectivity), int(ignore_index), sigma)
-    loss._medt_border_out = bout
-    return loss
+    return _seg_term(BORDER, logits, target, w0, None, fg, ignore_index, int(connectivity), sigma)
 
 
 def seg_border_loss(logits, target, w0, sigma=5.0, weight=None, ce=1.0, dice=0.0, eps=1.0, fg=1, connectivity=8, ignore_index=-100):
@@ -757,26 +715,7 @@ def seg_border_loss(logits, target, w0, sigma=5.0, weight=None, ce=1.0, dice=0.0
     bit.  loss._medt_ce_out is the region term's `out` (so TrainStep.check_targets() works as with seg_loss),
     loss._medt_border_out = [loss, R, w0, ...]."""
     w0, sigma = _border_args("seg_border_loss", logits, target, w0, sigma, fg, connectivity)
-    K = logits.shape[1]
-    if weight is not None:
-        if (not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.dim() != 1 or weight.numel() != K
-                or weight.device != logits.device):
-            raise L.MedtError(f"seg_border_loss: weight must be a float32 tensor of {K} class weights on the logits' device")
-        weight = weight.detach().contiguous()
-    ce, dice, eps = float(ce), float(dice), float(eps)
-    if ce == 0.0 and dice == 0.0:
-        raise L.MedtError("seg_border_loss: no region term (ce == dice == 0): border_loss() is the term alone")
-    if dice != 0.0 and not 2 <= K <= 8:
-        raise L.MedtError(f"seg_border_loss: soft Dice needs 2 <= K <= 8 classes (K = {K})")
-    if not eps >= 0.0:
-        raise L.MedtError("seg_border_loss: eps >= 0 expected")
-    loss, bout, rout = SegBorderFn.apply(logits, target, w0, weight, ce, dice, eps, int(fg), int(connectivity), int(ignore_index),
-                                         sigma)
-    loss._medt_ce_out = rout
-    loss._medt_border_out = bout
-    if CHECK_TARGETS and not torch.cuda.is_current_stream_capturing():
-        raise_on_bad_targets(rout, K)
-    return loss
+    return _seg_term(BORDER, logits, target, w0, (weight, ce, dice, eps), fg, ignore_index, int(connectivity), sigma)
 
 
 # --------------------------------------------------------------------------- #

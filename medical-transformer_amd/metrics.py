@@ -24,7 +24,19 @@ class LogNLLLoss(_WeightedLoss):
         return medt_amd.cross_entropy(y_input, y_target, self.ignore_index)
 
 
-class DiceCELoss(torch.nn.Module):
+class _RegionCriterion(torch.nn.Module):
+    """What the criteria around medt_amd.seg_loss and its relatives share: the class weights as the buffer `weight` (None without)
+    and the region term's ce / dice / eps / ignore_index."""
+
+    def __init__(self, weight, ce, dice, eps, ignore_index):
+        super().__init__()
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32).reshape(-1)
+        self.register_buffer("weight", weight)
+        self.ce, self.dice, self.eps, self.ignore_index = float(ce), float(dice), float(eps), ignore_index
+
+
+class DiceCELoss(_RegionCriterion):
     """ce * (class-weighted) cross entropy + dice * soft Dice, one kernel pair (medt_amd.seg_loss has the formulas).
 
     The Dice term is per image and per class over the non-ignored pixels, 2 <= K <= 8 classes; `eps` keeps empty images and
@@ -32,18 +44,14 @@ class DiceCELoss(torch.nn.Module):
     weighted cross entropy is a mean of per-rank weighted means, as with DistributedDataParallel."""
 
     def __init__(self, weight=None, ce=1.0, dice=1.0, eps=1.0, ignore_index=-100):
-        super().__init__()
-        if weight is not None:
-            weight = torch.as_tensor(weight, dtype=torch.float32).reshape(-1)
-        self.register_buffer("weight", weight)
-        self.ce, self.dice, self.eps, self.ignore_index = float(ce), float(dice), float(eps), ignore_index
+        super().__init__(weight, ce, dice, eps, ignore_index)
 
     def forward(self, y_input, y_target):
         return medt_amd.seg_loss(y_input, y_target, weight=self.weight, ce=self.ce, dice=self.dice, eps=self.eps,
                                  ignore_index=self.ignore_index)
 
 
-class BoundaryLoss(torch.nn.Module):
+class BoundaryLoss(_RegionCriterion):
     """ce * (class-weighted) cross entropy + dice * soft Dice + alpha * boundary loss (Kervadec et al., MIDL 2019) of the
     class `fg`: medt_amd.seg_boundary_loss has the formulas.  The signed distance map comes from the label map the step holds
     on the device (after the device-side augmentation, where there is one), not from the dataset.
@@ -52,12 +60,9 @@ class BoundaryLoss(torch.nn.Module):
     so a captured step follows the schedule without another capture."""
 
     def __init__(self, alpha=0.01, weight=None, ce=1.0, dice=0.0, eps=1.0, fg=1, ignore_index=-100):
-        super().__init__()
-        if weight is not None:
-            weight = torch.as_tensor(weight, dtype=torch.float32).reshape(-1)
-        self.register_buffer("weight", weight)
+        super().__init__(weight, ce, dice, eps, ignore_index)
         self.register_buffer("alpha", torch.full((1,), float(alpha), dtype=torch.float32))
-        self.ce, self.dice, self.eps, self.fg, self.ignore_index = float(ce), float(dice), float(eps), int(fg), ignore_index
+        self.fg = int(fg)
 
     def set_alpha(self, v):
         self.alpha.fill_(float(v))
@@ -67,7 +72,7 @@ class BoundaryLoss(torch.nn.Module):
                                           eps=self.eps, fg=self.fg, ignore_index=self.ignore_index)
 
 
-class BorderLoss(torch.nn.Module):
+class BorderLoss(_RegionCriterion):
     """ce * (class-weighted) cross entropy + dice * soft Dice + w0 * the border term for touching objects (the weight map of
     Ronneberger et al., U-Net, 2015, w0 exp(-(d1 + d2)^2 / (2 sigma^2)), applied to the cross entropy of the pixels between two
     objects of the class `fg`): medt_amd.seg_border_loss has the formulas.  The objects are the connected components of the label
@@ -77,13 +82,9 @@ class BorderLoss(torch.nn.Module):
     captured step follows a change without another capture."""
 
     def __init__(self, w0=10.0, sigma=5.0, weight=None, ce=1.0, dice=0.0, eps=1.0, fg=1, connectivity=8, ignore_index=-100):
-        super().__init__()
-        if weight is not None:
-            weight = torch.as_tensor(weight, dtype=torch.float32).reshape(-1)
-        self.register_buffer("weight", weight)
+        super().__init__(weight, ce, dice, eps, ignore_index)
         self.register_buffer("w0", torch.full((1,), float(w0), dtype=torch.float32))
-        self.sigma, self.ce, self.dice, self.eps = float(sigma), float(ce), float(dice), float(eps)
-        self.fg, self.connectivity, self.ignore_index = int(fg), int(connectivity), ignore_index
+        self.sigma, self.fg, self.connectivity = float(sigma), int(fg), int(connectivity)
 
     def set_w0(self, v):
         self.w0.fill_(float(v))

@@ -86,10 +86,16 @@ parser.add_argument('--border_connectivity', default=None, type=int, choices=[4,
 NUM_CLASSES = 2          # every network of lib.models ends in a 2-channel adjust convolution
 
 
+def split_loss(loss):
+    """--loss -> (region, extra): "ce", "dice" or "ce+dice", and None, "boundary" or "border"."""
+    region, _, extra = loss.rpartition("+")
+    return (region, extra) if extra in ("boundary", "border") else (loss, None)
+
+
 def make_boundary(loss, alpha, step, vmax):
     """None without a +boundary loss, else the schedule of the boundary term's weight: alpha in the first epoch, + step after
     every epoch, at most max."""
-    if not loss.endswith("+boundary"):
+    if split_loss(loss)[1] != "boundary":
         if alpha is not None or step is not None or vmax is not None:
             raise SystemExit("--boundary_alpha / --boundary_step / --boundary_max belong to the boundary loss: "
                              "use --loss ce+boundary, dice+boundary or ce+dice+boundary")
@@ -106,7 +112,7 @@ def boundary_alpha(sched, epoch):
 
 def make_border(loss, w0, sigma, connectivity):
     """None without a +border loss, else the settings of the border term: its weight, its width, the objects' connectivity."""
-    if not loss.endswith("+border"):
+    if split_loss(loss)[1] != "border":
         if w0 is not None or sigma is not None or connectivity is not None:
             raise SystemExit("--border_w0 / --border_sigma / --border_connectivity belong to the border term: "
                              "use --loss ce+border, dice+border or ce+dice+border")
@@ -120,8 +126,7 @@ def make_border(loss, w0, sigma, connectivity):
 
 def make_criterion(loss, class_weights, boundary=None, border=None):
     weight = None
-    region = loss[:-len("+boundary")] if loss.endswith("+boundary") else loss
-    region = region[:-len("+border")] if region.endswith("+border") else region
+    region, extra = split_loss(loss)
     if class_weights is not None:
         try:
             weight = [float(w) for w in class_weights.split(",")]
@@ -132,16 +137,15 @@ def make_criterion(loss, class_weights, boundary=None, border=None):
         if region == "dice":
             raise SystemExit("--class_weights weigh the cross entropy: use --loss ce or ce+dice")
         weight = torch.tensor(weight, dtype=torch.float32)
-    if loss.endswith("+border"):
+    scales = {"weight": weight, "ce": 0.0 if region == "dice" else 1.0, "dice": 0.0 if region == "ce" else 1.0}
+    if extra == "border":
         border = make_border(loss, None, None, None) if border is None else border
-        return BorderLoss(w0=border["w0"], sigma=border["sigma"], connectivity=border["connectivity"], weight=weight,
-                          ce=0.0 if region == "dice" else 1.0, dice=0.0 if region == "ce" else 1.0)
-    if region != loss:
-        return BoundaryLoss(alpha=0.01 if boundary is None else boundary["alpha"], weight=weight, ce=0.0 if region == "dice" else 1.0,
-                            dice=0.0 if region == "ce" else 1.0)
+        return BorderLoss(w0=border["w0"], sigma=border["sigma"], connectivity=border["connectivity"], **scales)
+    if extra == "boundary":
+        return BoundaryLoss(alpha=0.01 if boundary is None else boundary["alpha"], **scales)
     if loss == "ce":
         return LogNLLLoss() if weight is None else LogNLLLoss(weight=weight)         # the defaults: reference train.py:110
-    return DiceCELoss(weight=weight, ce=0.0 if loss == "dice" else 1.0, dice=1.0)
+    return DiceCELoss(**scales)
 
 
 def make_augment(aug, aug_jitter, aug_affine, aug_elastic=None, aug_elastic_grid=None, aug_elastic_sigma=None):
