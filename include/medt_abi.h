@@ -41,7 +41,8 @@ extern "C" {
  * number: additions only, nothing that version 11 declared was removed or changed, so a caller built against the earlier
  * header keeps working.  medt_label_boxes and medt_pair_hausdorff were added under the same number, in the same way.
  * medt_signed_edt and the medt_boundary_* entry points were added under the same number, in the same way.  medt_object_edt2
- * and the medt_border_* entry points were added under the same number, in the same way.  medt_augment_warp was added under
+ * and the medt_border_* entry points were added under the same number, in the same way.  The medt_split_* and medt_grow_*
+ * entry points were added under the same number, in the same way.  medt_augment_warp was added under
  * the same number, in the same way. */
 #define MEDT_ABI_VERSION 11
 
@@ -666,6 +667,55 @@ int medt_label_boxes(const int32_t* labels, int32_t* box, int N, int H, int W, i
 int medt_pair_hausdorff(const int32_t* la, const int32_t* lb, const int32_t* jobs, int32_t* scratch, int32_t* out, int n_jobs,
                         int col_blocks, int row_blocks, size_t scratch_elems, int n_out, int clear_out, int N, int H, int W,
                         void* stream);
+
+/* Splitting touching objects of a mask: peak markers of the distance transform and marker-controlled growth -- the building
+ * blocks of medt_amd.ops.split_markers / grow_labels / split_objects and of test.py --split, added under version 11 as the calls
+ * above were.  All integers; every result is independent of the order work-items and workgroups run in.
+ *
+ * medt_split_cmax: depth2 (N,H,W) int32 squared depths (medt_edt_* of the complement mask), comp (N,H,W) int32 component labels
+ * with values in [0, stride) -> cmax (N,stride) int32, cmax[n,l] = the largest depth2 over component l >= 1 (slot 0 and a label
+ * without a pixel hold 0).  The call clears the table itself.  Integer atomicMax, reduced per workgroup in LDS first.
+ * stride <= max_count is MEDT_EINVAL.
+ *
+ * medt_split_markers: -> marker (N,H,W) uint8, 255 at the marker pixels, 0 elsewhere.  With M(p) the maximum of depth2 over the
+ * (2 distance + 1)^2 window centred on p (pixels beyond the image count 0), a pixel with comp > 0 is a marker when
+ * sqrt(M) - sqrt(depth2) <= tolerance -- evaluated exactly in int64: e = M - depth2 - tolerance^2, e <= 0 or
+ * e^2 <= 4 tolerance^2 depth2 -- or when depth2 == cmax[n, comp].  One workgroup per MEDT_LABEL_TILE_H x MEDT_LABEL_TILE_W tile
+ * with the tile and its halo in LDS, the maximum taken separably.  1 <= distance <= MEDT_SPLIT_MAX_DISTANCE and
+ * 0 <= tolerance <= MEDT_SPLIT_MAX_TOLERANCE (MEDT_EINVAL otherwise).
+ *
+ * medt_grow_*: every pixel of mask != 0 takes the label of the seed at the smallest geodesic distance (steps at `connectivity`
+ * through the mask), ties to the smallest label; a pixel no seed reaches takes 0.  The workspace
+ * (medt_grow_workspace_bytes(N,H,W) bytes, a multiple of 16, 16-byte aligned) holds one packed 64-bit key (distance << 32 | label) per pixel and
+ * two int32 flags per tile.
+ *   medt_grow_init    seeds (N,H,W) int32 (> 0: a seed with that label; anything else: none), mask (N,H,W) uint8 -> the keys.
+ *                     A seed outside the mask is ignored (the caller refuses it).
+ *   medt_grow_passes  n_passes (1 .. MEDT_GROW_MAX_PASSES) relaxation passes, numbered first_pass, first_pass + 1, ...
+ *                     (first_pass >= 0: 0 directly behind medt_grow_init, then the passes issued so far).  One workgroup per tile
+ *                     relaxes its tile and a 1-pixel halo in LDS until a sweep changes nothing (at most (TILE_H + 2) (TILE_W + 2)
+ *                     sweeps) and stores its own pixels only; a tile whose own and eight neighbours' keys did not change in the
+ *                     pass before exits at once.  changed: n_passes int32 of device memory, changed[i] = 1 when pass i lowered a
+ *                     key, else 0 (the call clears them first).  The growth is complete behind the first pass that changed
+ *                     nothing; further passes leave everything as it is.  No workgroup waits on another.
+ *   medt_grow_labels  -> labels (N,H,W) int32 and, when dist is not NULL, dist (N,H,W) int32: the number of steps to the seed,
+ *                     -1 where no seed was reached or outside the mask.
+ * Limits and checks as medt_label_*: 1 <= H, W <= MEDT_LABEL_MAX_DIM, N*H*W below 2^31 (MEDT_EUNSUPPORTED), null pointers and a
+ * connectivity other than 4 or 8 MEDT_EINVAL, a smaller workspace_bytes MEDT_EWORKSPACE.  Element accesses only: no alignment
+ * beyond the elements' own (the workspace apart). */
+#define MEDT_SPLIT_MAX_DISTANCE  32
+#define MEDT_SPLIT_MAX_TOLERANCE 8
+#define MEDT_GROW_MAX_PASSES     64
+int medt_split_cmax(const int32_t* depth2, const int32_t* comp, int32_t* cmax, int N, int H, int W, int stride, int max_count,
+                    void* stream);
+int medt_split_markers(const int32_t* depth2, const int32_t* comp, const int32_t* cmax, uint8_t* marker, int N, int H, int W,
+                       int stride, int distance, int tolerance, void* stream);
+size_t medt_grow_workspace_bytes(int N, int H, int W);       /* 0 for a geometry the calls refuse */
+int medt_grow_init(const int32_t* seeds, const uint8_t* mask, void* workspace, size_t workspace_bytes, int N, int H, int W,
+                   void* stream);
+int medt_grow_passes(void* workspace, size_t workspace_bytes, int32_t* changed, int n_passes, int first_pass, int N, int H, int W,
+                     int connectivity, void* stream);
+int medt_grow_labels(const void* workspace, size_t workspace_bytes, int32_t* labels, int32_t* dist, int N, int H, int W,
+                     void* stream);
 
 #ifdef __cplusplus
 }

@@ -1323,10 +1323,76 @@ int medt_pair_hausdorff(const int32_t* la, const int32_t* lb, const int32_t* job
                           (hipStream_t)stream);
 }
 
+// medt_split_* / medt_grow_*: the geometry of the label calls
+int medt_split_cmax(const int32_t* depth2, const int32_t* comp, int32_t* cmax, int N, int H, int W, int stride, int max_count,
+                    void* stream) {
+    if (const int rc = label_geometry("split_cmax", N, H, W)) return rc;
+    if (!depth2 || !comp || !cmax) { set_error("split_cmax: null depth2, comp or cmax"); return MEDT_EINVAL; }
+    if (max_count < 0 || stride <= max_count) {
+        set_error("split_cmax: stride %d cannot hold the labels 0..%d", stride, max_count); return MEDT_EINVAL;
+    }
+    return split_cmax(depth2, comp, cmax, N, H, W, stride, (hipStream_t)stream);
+}
+
+int medt_split_markers(const int32_t* depth2, const int32_t* comp, const int32_t* cmax, uint8_t* marker, int N, int H, int W,
+                       int stride, int distance, int tolerance, void* stream) {
+    if (const int rc = label_geometry("split_markers", N, H, W)) return rc;
+    if (!depth2 || !comp || !cmax || !marker) { set_error("split_markers: null depth2, comp, cmax or marker"); return MEDT_EINVAL; }
+    if (stride < 1) { set_error("split_markers: stride %d", stride); return MEDT_EINVAL; }
+    if (distance < 1 || distance > MEDT_SPLIT_MAX_DISTANCE) {
+        set_error("split_markers: distance %d (1 .. %d)", distance, MEDT_SPLIT_MAX_DISTANCE); return MEDT_EINVAL;
+    }
+    if (tolerance < 0 || tolerance > MEDT_SPLIT_MAX_TOLERANCE) {
+        set_error("split_markers: tolerance %d (0 .. %d)", tolerance, MEDT_SPLIT_MAX_TOLERANCE); return MEDT_EINVAL;
+    }
+    return split_markers(depth2, comp, cmax, marker, N, H, W, stride, distance, tolerance, (hipStream_t)stream);
+}
+
+size_t medt_grow_workspace_bytes(int N, int H, int W) {
+    if (label_geometry("grow_workspace_bytes", N, H, W)) return 0;
+    return grow_workspace_bytes(N, H, W);
+}
+
+static int grow_workspace(const char* what, const void* workspace, size_t workspace_bytes, int N, int H, int W) {
+    if (const int rc = label_geometry(what, N, H, W)) return rc;
+    if (!workspace) { set_error("%s: null workspace", what); return MEDT_EINVAL; }
+    if ((uintptr_t)workspace % 16) { set_error("%s: the workspace must be 16-byte aligned", what); return MEDT_EINVAL; }
+    const size_t need = grow_workspace_bytes(N, H, W);
+    if (workspace_bytes < need) { set_error("workspace too small: need %zu", need); return MEDT_EWORKSPACE; }
+    return MEDT_OK;
+}
+
+int medt_grow_init(const int32_t* seeds, const uint8_t* mask, void* workspace, size_t workspace_bytes, int N, int H, int W,
+                   void* stream) {
+    if (const int rc = grow_workspace("grow_init", workspace, workspace_bytes, N, H, W)) return rc;
+    if (!seeds || !mask) { set_error("grow_init: null seeds or mask"); return MEDT_EINVAL; }
+    return grow_init(seeds, mask, workspace, N, H, W, (hipStream_t)stream);
+}
+
+int medt_grow_passes(void* workspace, size_t workspace_bytes, int32_t* changed, int n_passes, int first_pass, int N, int H, int W,
+                     int connectivity, void* stream) {
+    if (const int rc = grow_workspace("grow_passes", workspace, workspace_bytes, N, H, W)) return rc;
+    if (!changed) { set_error("grow_passes: null changed"); return MEDT_EINVAL; }
+    if (connectivity != 4 && connectivity != 8) { set_error("grow_passes: connectivity %d (4 or 8)", connectivity); return MEDT_EINVAL; }
+    if (n_passes < 1 || n_passes > MEDT_GROW_MAX_PASSES || first_pass < 0) {
+        set_error("grow_passes: %d passes from pass %d (1 .. %d passes, from 0 on)", n_passes, first_pass, MEDT_GROW_MAX_PASSES);
+        return MEDT_EINVAL;
+    }
+    return grow_passes(workspace, changed, n_passes, first_pass, N, H, W, connectivity, (hipStream_t)stream);
+}
+
+int medt_grow_labels(const void* workspace, size_t workspace_bytes, int32_t* labels, int32_t* dist, int N, int H, int W,
+                     void* stream) {
+    if (const int rc = grow_workspace("grow_labels", workspace, workspace_bytes, N, H, W)) return rc;
+    if (!labels || labels == dist) { set_error("grow_labels: null labels, or dist is labels"); return MEDT_EINVAL; }
+    return grow_unpack(workspace, labels, dist, N, H, W, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 #ifdef MEDT_LANE_EMU
 // The lane emulator builds a fixed list of translation units (tests/test_lane_emu.py); label.hip, which the product compiles as
-// a unit of its own (medt_amd/build.py), reaches the emulated library through this one, as it stands.
+// a unit of its own (medt_amd/build.py), reaches the emulated library through this one, as it stands, and so does split.hip.
 #include "label.hip"
+#include "split.hip"      // (behind label.hip: it uses that file's stand-ins for the integer atomics)
 #endif

@@ -161,6 +161,14 @@ int label_components(const uint8_t* mask, int32_t* labels, int32_t* count, void*
 int label_tables(const int32_t* labels, int32_t* area, uint8_t* frame, int N, int H, int W, int stride, hipStream_t s);
 int label_select(const int32_t* labels, const uint8_t* keep, const uint8_t* mask, uint8_t* out, int N, int H, int W, int stride,
                  hipStream_t s);
+// splitting touching objects: component maxima of the squared depth, peak markers, marker-controlled growth (split.hip; medt_abi.h)
+int split_cmax(const int32_t* depth2, const int32_t* comp, int32_t* cmax, int N, int H, int W, int stride, hipStream_t s);
+int split_markers(const int32_t* depth2, const int32_t* comp, const int32_t* cmax, uint8_t* marker, int N, int H, int W, int stride,
+                  int distance, int tolerance, hipStream_t s);
+size_t grow_workspace_bytes(int N, int H, int W);
+int grow_init(const int32_t* seeds, const uint8_t* mask, void* workspace, int N, int H, int W, hipStream_t s);
+int grow_passes(void* workspace, int32_t* changed, int n_passes, int first_pass, int N, int H, int W, int connectivity, hipStream_t s);
+int grow_unpack(const void* workspace, int32_t* labels, int32_t* dist, int N, int H, int W, hipStream_t s);
 // bounding boxes of the components; directed squared Hausdorff distances of pairs of them from a device job table (label.hip)
 int label_boxes(const int32_t* labels, int32_t* box, int N, int H, int W, int stride, hipStream_t s);
 int pair_hausdorff(const int32_t* la, const int32_t* lb, const int32_t* jobs, int32_t* scratch, int32_t* out, int n_jobs,

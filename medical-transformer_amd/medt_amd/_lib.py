@@ -179,6 +179,12 @@ SIGNATURES = {
     "medt_label_select": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
     "medt_label_boxes": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
     "medt_pair_hausdorff": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_size_t] + [C.c_int] * 5 + [C.c_void_p]),
+    "medt_split_cmax": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "medt_split_markers": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
+    "medt_grow_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "medt_grow_init": (C.c_int, [C.c_void_p] * 3 + [C.c_size_t] + [C.c_int] * 3 + [C.c_void_p]),
+    "medt_grow_passes": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "medt_grow_labels": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
 }
 
 

@@ -1233,3 +1233,111 @@ def pair_hausdorff_sq(la, ca, lb, cb, pairs, max_scratch_elems=None, boxes=None)
                                         int(colb[s:e].sum()), int(rows[s:e].sum()), scratch.numel(), J, int(k == 0), N, H, W,
                                         _stream()), "medt_pair_hausdorff")
     return out
+
+
+# --------------------------------------------------------------------------- #
+# splitting touching objects: peak markers of the depth map, marker-controlled growth (test.py --split)
+# --------------------------------------------------------------------------- #
+SPLIT_MAX_DISTANCE = 32            # MEDT_SPLIT_MAX_DISTANCE of include/medt_abi.h: the largest window radius
+SPLIT_MAX_TOLERANCE = 8            # MEDT_SPLIT_MAX_TOLERANCE
+GROW_MAX_PASSES = 64               # MEDT_GROW_MAX_PASSES: passes of one medt_grow_passes call
+GROW_BATCHES = (2, 4, 8, 16)       # passes issued per host read of their "changed" flags; the last size repeats
+
+
+def _split_args(what, distance, tolerance, connectivity):
+    if connectivity not in (4, 8):
+        raise L.MedtError(f"{what}: connectivity {connectivity!r} (4 or 8)")
+    if isinstance(distance, bool) or not isinstance(distance, int) or not 1 <= distance <= SPLIT_MAX_DISTANCE:
+        raise L.MedtError(f"{what}: distance {distance!r} (an integer window radius, 1 .. {SPLIT_MAX_DISTANCE})")
+    if isinstance(tolerance, bool) or not isinstance(tolerance, int) or not 0 <= tolerance <= SPLIT_MAX_TOLERANCE:
+        raise L.MedtError(f"{what}: tolerance {tolerance!r} (an integer number of pixels, 0 .. {SPLIT_MAX_TOLERANCE})")
+
+
+def _split_markers(m, distance, tolerance, connectivity):
+    """Steps 1 to 5 of DESIGN.md 'Splitting touching objects' on a contiguous (N,H,W) uint8 mask -> uint8 {0,255} markers."""
+    N, H, W = m.shape
+    comp, cnt = label(m, connectivity)
+    depth2 = edt_sq((m == 0).to(torch.uint8))
+    top = int(cnt.max())                                       # (one host sync, as label_tables)
+    stride = top + 1
+    cmax = torch.empty(N, stride, device=m.device, dtype=torch.int32)
+    marker = torch.empty(N, H, W, device=m.device, dtype=torch.uint8)
+    lib = L.lib()
+    L.check(lib.medt_split_cmax(depth2.data_ptr(), comp.data_ptr(), cmax.data_ptr(), N, H, W, stride, top, _stream()),
+            "medt_split_cmax")
+    L.check(lib.medt_split_markers(depth2.data_ptr(), comp.data_ptr(), cmax.data_ptr(), marker.data_ptr(), N, H, W, stride,
+                                   distance, tolerance, _stream()), "medt_split_markers")
+    return marker
+
+
+def split_markers(mask, distance=7, tolerance=1, connectivity=8):
+    """uint8 (N,H,W) or (H,W) mask -> uint8 {0,255} marker mask of the same shape.  With depth2 the exact squared distance of a
+    pixel of mask != 0 to the nearest pixel of its image outside the mask (EDT_NONE in an image without one) and M the maximum of
+    depth2 over the (2 distance + 1)^2 window around the pixel, clipped to the image, a pixel of the mask is a marker when
+    sqrt(M) - sqrt(depth2) <= tolerance (evaluated exactly in integers) or when depth2 is the maximum of its component at
+    `connectivity`: every component holds a marker.  distance 1 .. 32, tolerance 0 .. 8, both integers."""
+    (m,) = _edt_masks("split_markers", mask)
+    _split_args("split_markers", distance, tolerance, connectivity)
+    return _split_markers(m, distance, tolerance, connectivity).reshape(mask.shape)
+
+
+def _grow(seeds, m, connectivity, labels, dist=None):
+    """The growth on contiguous (N,H,W) maps into `labels` (and `dist`) -> the number of passes issued up to and including the
+    first that changed nothing."""
+    N, H, W = m.shape
+    lib = L.lib()
+    need = lib.medt_grow_workspace_bytes(N, H, W)              # (0 for a geometry the call below refuses, with the reason)
+    workspace = torch.empty(max(need // 8, 2), device=m.device, dtype=torch.int64)          # (need is a multiple of 16)
+    L.check(lib.medt_grow_init(seeds.data_ptr(), m.data_ptr(), workspace.data_ptr(), need, N, H, W, _stream()), "medt_grow_init")
+    changed = torch.empty(GROW_MAX_PASSES, device=m.device, dtype=torch.int32)
+    issued, limit, batch, passes = 0, H * W + 1, 0, None
+    while passes is None:
+        if issued >= limit:
+            raise L.MedtError(f"grow_labels: no fixed point after {issued} passes over {H} x {W} maps")
+        k = min(GROW_BATCHES[min(batch, len(GROW_BATCHES) - 1)], limit - issued)
+        L.check(lib.medt_grow_passes(workspace.data_ptr(), need, changed.data_ptr(), k, issued, N, H, W, int(connectivity),
+                                     _stream()), "medt_grow_passes")
+        flags = changed[:k].cpu().tolist()                     # one host read per batch
+        if 0 in flags:
+            passes = issued + flags.index(0) + 1
+        issued += k
+        batch += 1
+    L.check(lib.medt_grow_labels(workspace.data_ptr(), need, labels.data_ptr(), L.ptr(dist), N, H, W, _stream()), "medt_grow_labels")
+    return passes
+
+
+def grow_labels(seeds, mask, connectivity=8, out=None, return_passes=False, return_distance=False):
+    """int32 seed map and uint8 mask, both (N,H,W) or (H,W) -> int32 labels of the same shape: every pixel of mask != 0 takes the
+    label of the seed (a pixel with seeds > 0) at the smallest geodesic distance -- the fewest steps at `connectivity` through
+    the mask -- ties to the smallest label; a component of the mask without a seed stays 0, and so does everything outside the
+    mask.  Negative seeds and seeds outside the mask are refused (one host sync).  The same bits on every run.  out: a
+    contiguous int32 tensor to write into (any alignment).  return_passes: also the number of device passes up to and including
+    the first that changed nothing; return_distance: also the int32 map of step counts (-1 where no seed was reached)."""
+    (m,) = _edt_masks("grow_labels", mask)
+    if connectivity not in (4, 8):
+        raise L.MedtError(f"grow_labels: connectivity {connectivity!r} (4 or 8)")
+    if seeds.dtype != torch.int32 or tuple(seeds.shape) != tuple(mask.shape) or seeds.device != mask.device:
+        raise L.MedtError("grow_labels: seeds must be an int32 map of the mask's shape on its device")
+    sd = seeds.contiguous().reshape(m.shape)
+    if bool(((sd < 0) | ((sd != 0) & (m == 0))).any()):
+        raise L.MedtError("grow_labels: a negative seed or a seed outside the mask")
+    labels = _edt_out("grow_labels", out, mask)
+    dist = torch.empty(m.shape, device=m.device, dtype=torch.int32) if return_distance else None
+    passes = _grow(sd, m, connectivity, labels, dist)
+    res = (labels,) + ((passes,) if return_passes else ()) + ((dist.reshape(mask.shape),) if return_distance else ())
+    return res[0] if len(res) == 1 else res
+
+
+def split_objects(mask, distance=7, tolerance=1, connectivity=8, out=None):
+    """uint8 (N,H,W) or (H,W) mask -> (labels, counts): the objects of mask != 0 with touching ones split.  The markers of
+    split_markers are labelled at `connectivity` (K = counts[n] of them, numbered in raster order of their first pixel) and every
+    pixel of the mask takes the label of the marker at the smallest geodesic distance, ties to the smallest label (grow_labels).
+    labels: int32 of the mask's shape, 0 outside the mask and 1..K inside, every label's pixels connected and inside one
+    component of the mask; a component with a single marker comes back whole.  counts: int32 (N,).  All integers, the same bits
+    on every run.  out: a contiguous int32 tensor to write the labels into (any alignment)."""
+    (m,) = _edt_masks("split_objects", mask)
+    _split_args("split_objects", distance, tolerance, connectivity)
+    labels = _edt_out("split_objects", out, mask)
+    seeds, counts = label(_split_markers(m, distance, tolerance, connectivity), connectivity)
+    _grow(seeds, m, connectivity, labels)
+    return labels, counts

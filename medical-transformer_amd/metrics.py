@@ -240,16 +240,21 @@ def _object_scores_image(ap, ag, rows):
 def _object_tables(pred, target, connectivity, labelled):
     """What object_scores and object_hausdorff both start from -> (label maps (lp, lg), object counts on the device (cp, cg),
     the counts as lists, the area tables on the host, the overlap rows (n, j, i, |G_i ∩ P_j|) as a list).  Masks are labelled here
-    at `connectivity`; with labelled=True the label maps are taken as given and the counts are their maxima."""
+    at `connectivity`; with labelled=True the label maps are taken as given and the counts are their maxima.  labelled may also
+    be a pair (pred_is_labelled, target_is_labelled): one side a label map, the other a mask."""
     from medt_amd import ops
-    if labelled:
-        lp, lg = pred, target
-        N = lp.reshape(-1, *lp.shape[-2:]).shape[0]
-        cp = lp.reshape(N, -1).amax(dim=1).to(torch.int32)
-        cg = lg.reshape(N, -1).amax(dim=1).to(torch.int32)
-    else:
-        lp, cp = ops.label(pred, connectivity)
-        lg, cg = ops.label(target, connectivity)
+    if isinstance(labelled, (bool, int)):
+        labelled = (bool(labelled),) * 2
+    if not isinstance(labelled, (tuple, list)) or len(labelled) != 2:
+        raise ValueError(f"labelled: {labelled!r}: a bool, or a pair (pred_is_labelled, target_is_labelled)")
+
+    def side(x, given):
+        if not given:
+            return ops.label(x, connectivity)
+        N = x.reshape(-1, *x.shape[-2:]).shape[0]
+        return x, x.reshape(N, -1).amax(dim=1).to(torch.int32)
+
+    (lp, cp), (lg, cg) = side(pred, labelled[0]), side(target, labelled[1])
     area_p, _ = ops.label_tables(lp, cp)
     area_g, _ = ops.label_tables(lg, cg)
     rows = ops.label_overlaps(lp, cp, lg, cg).cpu().tolist()
@@ -259,7 +264,8 @@ def _object_tables(pred, target, connectivity, labelled):
 def object_scores(pred, target, connectivity=8, labelled=False):
     """Per-image object-level scores of a prediction against a target, on the device.  pred / target: uint8 masks (N,H,W) or
     (H,W), foreground = mask != 0, labelled here at `connectivity` (4 or 8; 8 is MATLAB's bwlabel); or with labelled=True int32
-    label maps with consecutive labels 1..K per image, taken as given (instance annotations).
+    label maps with consecutive labels 1..K per image, taken as given (instance annotations, medt_amd.ops.split_objects);
+    labelled=(pred_is_labelled, target_is_labelled) says so per side.
 
     With P_j the predicted objects, G_i the target objects, I[i,j] = |G_i ∩ P_j|, ties to the lowest index:
       f1    GlaS object F1: P_j is a true positive when the G_i* it overlaps most has 2 I[i*,j] >= |G_i*|; FP = Kp - TP,
@@ -317,7 +323,8 @@ def _hausdorff_candidates(boxes_own, boxes_other, own, others, partner):
 
 def object_hausdorff(pred, target, connectivity=8, labelled=False, prune=True):
     """Per-image object-level Hausdorff distance of GlaS (Sirinukunwattana et al.), on the device.  pred / target as in
-    object_scores: uint8 masks labelled here at `connectivity`, or with labelled=True int32 label maps taken as given.
+    object_scores: uint8 masks labelled here at `connectivity`, or with labelled=True int32 label maps taken as given, or per
+    side with labelled=(pred_is_labelled, target_is_labelled).
 
     With G_i the target objects and S_j the predicted ones,
       H(A,B) = max(max_{x in A} min_{y in B} |x-y|, max_{y in B} min_{x in A} |x-y|), Euclidean, in pixels, over ALL pixels of

@@ -6,7 +6,9 @@ undefined args.aug (test.py:62) and dies; here the flag exists and is ignored.  
 (HD, HD95, ASSD) of the written masks behind the F1 / mIoU / PA line, --objects on the object-level scores (object F1 and Dice,
 AJI, PQ) behind those, --object_hausdorff on the object-level Hausdorff distance of GlaS behind those; --fill_holes on and
 --min_object AREA clean the masks on the device before they are written and scored; --tta flips|d4 averages the logits of the
-mirrored (and rotated) views of every image or window before the mask is taken (medt_amd.tta)."""
+mirrored (and rotated) views of every image or window before the mask is taken (medt_amd.tta); --split on splits touching
+objects of the cleaned mask on the device before --objects and --object_hausdorff count them (medt_amd.ops.split_objects),
+--instance_labels DIR gives those two scores ground-truth instances, --write_instances on writes the split label maps."""
 import argparse
 import os
 
@@ -76,6 +78,21 @@ parser.add_argument('--min_object', type=int, default=0, metavar='AREA',
 parser.add_argument('--fill_holes', default='off', choices=['off', 'on'],
                     help='(not in the reference) on: the holes of every mask are filled before small objects are removed and the '
                          'mask is written and scored (medt_amd.ops.fill_holes = scipy.ndimage.binary_fill_holes)')
+parser.add_argument('--split', default='off', choices=['off', 'on'],
+                    help='(not in the reference) on: touching objects of every mask are split on the device -- peak markers of the '
+                         'distance transform, marker-controlled growth (medt_amd.ops.split_objects) -- behind --fill_holes and '
+                         '--min_object, at --connectivity; --objects and --object_hausdorff score the split label map.  The PNG, '
+                         'the F1 / mIoU / PA line and --surface describe the same foreground and do not change')
+parser.add_argument('--split_distance', type=int, default=None, metavar='R',
+                    help='with --split on: radius of the window whose depth maximum makes a marker, 1 .. 32 pixels (default 7)')
+parser.add_argument('--split_tolerance', type=int, default=None, metavar='T',
+                    help='with --split on: a pixel within T pixels of depth of its window maximum is a marker, 0 .. 8 (default 1)')
+parser.add_argument('--instance_labels', type=str, default=None, metavar='DIR',
+                    help='(not in the reference) ground-truth instances for --objects and --object_hausdorff: DIR/<stem>.png (8- or '
+                         '16-bit, value = instance id, 0 = background) or DIR/<stem>.npy of the image\'s size; ids are renumbered '
+                         'in raster order of their first pixel.  Not with --crop')
+parser.add_argument('--write_instances', default='off', choices=['off', 'on'],
+                    help='(not in the reference) with --split on: also writes <stem>_inst.png, the split label map as a 16-bit PNG')
 
 # the score lines behind "images ...": (line prefix = the flag's name with a blank for its underscore, metric of a {0,255} mask
 # batch and a {0,1} target batch on the device -> per-batch dictionary with "valid", the keys the line shows, their labels)
@@ -105,16 +122,45 @@ def images_line(counts):
     return "images {}  F1 {:.4f}  mIoU {:.4f}  PA {:.4f}".format(len(f1), f1.mean().item(), iou.mean().item(), pa.mean().item())
 
 
-def summary_line(prefix, keys, labels, batches):
-    """One line of SUMMARY from its per-batch dictionaries: the means over the valid images, nan when there is none."""
+def summary_line(prefix, keys, labels, batches, totals=False):
+    """One line of SUMMARY from its per-batch dictionaries: the means over the valid images, nan when there is none.  totals:
+    behind them the objects counted on either side, summed over all images (the object lines under --split on or
+    --instance_labels, where the counts are what those flags change)."""
     valid = torch.cat([s["valid"] for s in batches])
     means = [v.mean().item() if len(v) else float("nan") for v in (torch.cat([s[k] for s in batches])[valid] for k in keys)]
-    return "{} images {}/{}".format(prefix, int(valid.sum()), len(valid)) + "".join(
+    line = "{} images {}/{}".format(prefix, int(valid.sum()), len(valid)) + "".join(
         "  {} {:.4f}".format(label, m) for label, m in zip(labels, means))
+    if totals:
+        line += "  Npred {}  Ngt {}".format(*(int(torch.cat([s[k] for s in batches]).sum()) for k in ("n_pred", "n_gt")))
+    return line
+
+
+def split_options(args):
+    """The checked --split* / --instance_labels / --write_instances flags -> (distance, tolerance) or None without --split on.
+    Refusals leave through parser.error before any file or device is touched."""
+    if args.split != "on":
+        for flag in ("split_distance", "split_tolerance"):
+            if getattr(args, flag) is not None:
+                parser.error("--%s: add --split on" % flag)
+        if args.write_instances == "on":
+            parser.error("--write_instances: add --split on")
+    distance = 7 if args.split_distance is None else args.split_distance
+    tolerance = 1 if args.split_tolerance is None else args.split_tolerance
+    if not 1 <= distance <= 32:
+        parser.error("--split_distance: %d: 1 .. 32 pixels" % distance)
+    if not 0 <= tolerance <= 8:
+        parser.error("--split_tolerance: %d: 0 .. 8 pixels" % tolerance)
+    if args.instance_labels is not None:
+        if args.crop is not None:
+            parser.error("--instance_labels: the instance maps have the images' own size: not with --crop")
+        if not os.path.isdir(args.instance_labels):
+            parser.error("--instance_labels: %s is not a directory" % args.instance_labels)
+    return (distance, tolerance) if args.split == "on" else None
 
 
 def main():
     args = parser.parse_args()
+    split = split_options(args)
     if args.gray == "yes":
         from utils_gray import JointTransform2D, ImageToImage2D
         imgchant = 1
@@ -141,6 +187,7 @@ def main():
     scores = []
     # the score lines asked for, each with its per-batch dictionaries of (mask, target > 0): eager, behind the replay
     scored = [(row, []) for row in SUMMARY if getattr(args, row[0].replace(" ", "_")) == "on"]
+    object_lines = any(row[0] != "surface" for row, _ in scored)      # the lines that count objects: what --split changes
 
     def clean(mask, target, like):
         """The clean-ups of a uint8 {0,255} mask batch on the device, holes first, and the {tp, fp, fn, tn} counts of the result
@@ -203,17 +250,38 @@ def main():
         if args.fill_holes == "on" or args.min_object > 0:
             mask, counts = clean(mask, target, counts)
         scores.append(counts)
+        objects = None
+        if split is not None and (object_lines or args.write_instances == "on"):
+            # the same foreground, its touching objects apart: what the object-level lines count and --write_instances writes
+            from medt_amd import ops
+            objects, _ = ops.split_objects(mask, split[0], split[1], args.connectivity)
         if scored:                 # the mask the PNG holds against target > 0
             t = (target > 0).to(torch.uint8)
-            for (_, metric, _, _), batches in scored:
-                batches.append(metric(mask, t, args.connectivity))
+            instances = None
+            if args.instance_labels is not None and object_lines:
+                import numpy
+                from medt_amd.instances import read_instances
+                instances = torch.from_numpy(numpy.stack([read_instances(args.instance_labels, it[2], tuple(mask.shape[1:]))[0]
+                                                          for it in items])).to(mask.device)
+            for (name, metric, _, _), batches in scored:
+                if name != "surface" and (objects is not None or instances is not None):
+                    batches.append(metric(mask if objects is None else objects, t if instances is None else instances,
+                                          args.connectivity, labelled=(objects is not None, instances is not None)))
+                else:
+                    batches.append(metric(mask, t, args.connectivity))
         mask = mask.cpu().numpy()
         for k, it in enumerate(items):
             imwrite(fulldir + it[2], mask[k])
+        if args.write_instances == "on":
+            from medt_amd.instances import write_instances
+            objects = objects.cpu().numpy()
+            for k, it in enumerate(items):
+                write_instances(fulldir + os.path.splitext(it[2])[0] + "_inst.png", objects[k])
     if scores:
         print(images_line(torch.cat(scores)))
         for (prefix, _, keys, labels), batches in scored:
-            print(summary_line(prefix, keys, labels, batches))
+            print(summary_line(prefix, keys, labels, batches,
+                               totals=prefix != "surface" and (split is not None or args.instance_labels is not None)))
 
 
 if __name__ == "__main__":
